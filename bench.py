@@ -15,7 +15,7 @@ post-LN + 2x2 merge) + cogs_project -- SURVEY.md section 8(d) "frames/sec encode
 N > 1: the clip's frames are sharded, rank r encodes and projects its contiguous slice, ONE RCCL all-gather
 reassembles the [M,3584] visual tokens in frame order on every rank (the LLM rank needs them all); time = max
 over ranks. The headline at EVERY N is the metric's own clip -- BASELINE configs[1], 64 frames -- so the N = 1, 2, 4, 8
-values are one STRONG-scaling curve of a fixed workload (32 / 16 / 8 frames per GPU). Side keys of the same line:
+values are one STRONG-scaling curve of a fixed workload (32 / 16 / 8 frames per GPU). Side keys of the line (--full):
   cfg3   BASELINE configs[2]: ONE 256-frame 480p clip (16 384-token budget -> 140x280 per frame, 200 patches / 50
          tokens per frame), frames sharded over the N ranks (32 per GPU at N = 8), one all-gather -- strong scaling
   weak   N > 1: the clip grows with N at 64 frames per GPU (every rank keeps the N = 1 workload; the only added cost is
@@ -24,7 +24,14 @@ values are one STRONG-scaling curve of a fixed workload (32 / 16 / 8 frames per 
 BASELINE configs[4]: every rank answers its OWN 64-frame clip through the whole product API (processor -> qa_selection
 -> generate), replicas only, no collective.
 
-The same JSON line also carries, measured after the timed steps on rank 0 at N = 1:
+A plain run sets up, warms up, times the K steps and prints the line: value (frames/s), ms_per_step, the config.
+`--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy (float32 / float64, <= 64 MB): the
+visual tokens' per-row sums and a fixed, seeded sample of whole rows (cfg5: the answer's token ids). Inputs and weights
+are seeded, so two builds run with the same arguments can be compared output for output.
+
+With `--full` the line also carries the side keys: `cfg3` / `weak` / `allgather` above, `roofline` and `breakdown_ms`
+(one extra step with HIP events around every launch), `shard8` and `stages`, and, measured after the timed steps on
+rank 0 at N = 1:
   answer_tokens_per_s   greedy decode rate of the Qwen2-7B path (prefill of the full ~15k-token
                         interleaved prompt, then 128 tokens, EOS ignored), e2e_s the whole answer latency;
   pipeline              wall time of CogStreamProcessor -> qa_selection -> generate (64 new tokens) through the product
@@ -262,9 +269,10 @@ class PromptLengthTokenizer:
 QUESTION = "What is happening in the video?"
 
 
-def pipeline_once(model, processor, dframes, new_tokens, expect_prompt=None):
+def pipeline_once(model, processor, dframes, new_tokens, expect_prompt=None, keep=None):
     """one answer through the product API, as evaluate/answer_generate.py:60-76 drives the reference: processor ->
-    qa_selection(mode="FCC") -> generate (greedy, EOS ignored, `new_tokens` tokens). -> stage split in seconds"""
+    qa_selection(mode="FCC") -> generate (greedy, EOS ignored, `new_tokens` tokens). -> stage split in seconds;
+    keep["ids"] = the generated ids when a dict is given"""
     import random
     random.seed(0)
     torch.manual_seed(0)
@@ -285,6 +293,8 @@ def pipeline_once(model, processor, dframes, new_tokens, expect_prompt=None):
     t2 = time.perf_counter()
     model.stage_times = None
     assert ids.shape == (1, new_tokens)
+    if keep is not None:
+        keep["ids"] = ids
     split = {"processor": t1 - t0, **{k: st.get(k, 0.0) for k in ("encode", "kmeans", "event_prefill", "answer_prefill", "decode")}}
     split["host_and_small_kernels"] = (t2 - t0) - sum(split.values())
     return {"total_s": round(t2 - t0, 4), "prompt_tokens": int(inputs["input_ids"].shape[1]),
@@ -381,12 +391,15 @@ def bench_cfg5(args, rank, world, dev, ranks_seen):
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    last = {}
     for _ in range(args.steps):
-        rec = pipeline_once(model, processor, dfr, new_tokens)
+        rec = pipeline_once(model, processor, dfr, new_tokens, keep=last)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"answer_token_ids": last["ids"].double().cpu().numpy()})
     if world > 1:
         tt = torch.tensor([dt], device="cpu" if dist.get_backend() == "gloo" else dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -403,6 +416,31 @@ def bench_cfg5(args, rank, world, dev, ranks_seen):
                        "frames": args.frames * world, "frames_per_gpu": args.frames,
                        "parallelism": "replicas only: every rank holds the whole model, no collective (evaluate/answer_generate.py:186-187)"},
             "pipeline_rank0": rec}
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_ROWS = 2048        # 2048 x 3584 fp32 = 29 MB
+
+
+def token_outputs(mm) -> dict:
+    """the [M, D] visual tokens of a step -> every row's fp64 sum, and a fixed, seeded sample of DUMP_ROWS whole rows
+    in fp32 with their row indices"""
+    rows = np.sort(np.random.default_rng(0).choice(mm.shape[0], size=min(mm.shape[0], DUMP_ROWS), replace=False))
+    host = mm.cpu()
+    return {"visual_tokens_row_sum": host.double().sum(1).numpy(),
+            "visual_tokens_rows": host[torch.from_numpy(rows)].float().numpy(),
+            "visual_tokens_row_index": rows.astype(np.float64)}
+
+
+def dump_outputs(dirname: str, arrays: dict) -> None:
+    """--dump-outputs: arrays -> dirname/<name>.npy, float32 / float64 only, DUMP_MAX_BYTES in all"""
+    arrays = {k: np.ascontiguousarray(v) for k, v in arrays.items()}
+    assert all(v.dtype in (np.float32, np.float64) for v in arrays.values()), {k: v.dtype for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_MAX_BYTES, total
+    os.makedirs(dirname, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), v)
 
 
 def launch_ranks(n: int) -> int:
@@ -463,7 +501,16 @@ def main() -> None:
     ap.add_argument("--emulate-shard", type=int, default=8,
                     help="N = 1 only: also time ONE rank's share (1/R of the frames) of the clip on this GPU and report "
                          "shard_efficiency = (t_clip / R) / t_shard (0 = off)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every side measurement (roofline pass, shard / cfg3 / weak curves, "
+                         "HBM stages, the all-gather alone, Qwen2 prefill + decode, product pipeline and session, GPU "
+                         "pre-processing, CPU baselines); without it a run times the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step as DIR/<name>.npy (float32 / float64, "
+                         f"<= {DUMP_MAX_BYTES >> 20} MB; a fixed, seeded sample of rows of a larger output)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     t_process0 = time.perf_counter()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -545,7 +592,7 @@ def main() -> None:
     n_patches, m_tokens = T * per_frame, T * P
     merge = torch.tensor([2])
     pix_all = None
-    if world == 1:
+    if world == 1 and args.full:          # host path: the 'preprocess' comparison and the CPU baseline's input
         t0 = time.perf_counter()
         host = processing.preprocess_videos([frames], merge_size=2, max_tokens=16384 * t_loc // (256 if cfg3 else 64))
         t_host_pre = time.perf_counter() - t0
@@ -596,6 +643,8 @@ def main() -> None:
     dt, mm = timed(step, args.warmup, args.steps)
     ms_per_step = dt / args.steps * 1e3
     fps = T * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, token_outputs(mm))
     gather_note = (f"one RCCL all-gather of the [M,{lcfg.hidden_size}] projected tokens" if wide else
                    f"one RCCL all-gather of the [M,{vcfg.hidden_size}] encoder tokens, projector on every rank")
 
@@ -614,15 +663,16 @@ def main() -> None:
                                   (f"; STRONG scaling over {world} GPUs: the same fixed clip as at N = 1, {t_loc} frames per GPU" if world > 1 else "")),
                    "scaling_note": ("WEAK scaling: the clip grows with N" if weak else
                                     "STRONG scaling: the workload is the same fixed clip at every N (the N = 1 line is this curve's "
-                                    "first point); side keys: 'cfg3' = BASELINE configs[2]'s 256-frame clip sharded the same way, "
+                                    "first point); side keys (--full): 'cfg3' = BASELINE configs[2]'s 256-frame clip sharded the same way, "
                                     "'weak' = 64 frames per GPU"),
                    "frames": T, "frames_per_gpu": t_loc, "patches": n_patches, "visual_tokens": m_tokens,
                    "parallelism": (f"frames sharded over {world} GPUs ({t_loc} each), encode+project per rank, {gather_note}")
                    if world > 1 else "single GPU"},
     }
 
+    # ---- side measurements beside the headline, --full only (the result line is printed at the end either way) ----
     # ---- N > 1: the all-gather on its own, both payloads (events on the stream the collective is queued from + wall) ----
-    if world > 1:
+    if world > 1 and args.full:
         from cogstream_amd.parallel import gather_rows
         counts = [(e - b) * P for b, e in frame_shards(T, world)]
         ag = {"backend": dist.get_backend(), "note": "the one data-path collective of a step, alone: all-gather of this clip's "
@@ -660,11 +710,12 @@ def main() -> None:
     h = enc.handle
     ms = (C.c_float * 4)()
     cnt = (C.c_int * 4)()
-    barrier()
-    L.check(L.lib.cogs_profile_begin(h.h))
-    step()
-    L.check(L.lib.cogs_profile_end(h.h, L.current_stream(), ms, cnt))
-    if rank == 0:
+    if args.full:
+        barrier()
+        L.check(L.lib.cogs_profile_begin(h.h))
+        step()
+        L.check(L.lib.cogs_profile_end(h.h, L.current_stream(), ms, cnt))
+    if rank == 0 and args.full:
         n_loc, m_proj = t_loc * per_frame, t_loc * P
         gflops = vit_gemm_flops(n_loc, m_proj, vcfg, lcfg.hidden_size)
         gemm_ms, gemm_n = float(ms[0]), int(cnt[0])
@@ -723,7 +774,7 @@ def main() -> None:
                 "note": "encode+project of one rank's frames on one GPU; the all-gather is not in it"}
 
     R = args.emulate_shard
-    if rank == 0 and world == 1 and R > 1 and T % R == 0:
+    if args.full and rank == 0 and world == 1 and R > 1 and T % R == 0:
         out["shard%d" % R] = shard_probe(pix, T, gh, gw, ms_per_step, R)
 
     # ---- side curves, every rank takes part, rank 0 reports ----
@@ -741,7 +792,7 @@ def main() -> None:
         return rec, c, mm_, dt_ / n
 
     # BASELINE configs[2]: one 256-frame clip at the 16384-token budget, frames sharded over the ranks (32 per GPU at N = 8)
-    if not cfg3 and not args.no_cfg3 and args.frames == 64 and not weak:
+    if args.full and not cfg3 and not args.no_cfg3 and args.frames == 64 and not weak:
         rec3, c3, mm3, t3 = side_curve(256, 256, "BASELINE configs[2]")
         rec3["scaling"] = "strong"
         if rank == 0:
@@ -752,7 +803,7 @@ def main() -> None:
             out["stages"] = stage_rooflines(c3, mm3, dev, with_cpu=not args.no_cpu)
         del c3, mm3
     # the weak curve: 64 frames per GPU (N = 4 is a 256-frame clip at cfg2's frame size)
-    if world > 1 and not cfg3 and not weak and args.frames == 64:
+    if args.full and world > 1 and not cfg3 and not weak and args.frames == 64:
         recw, cw, mmw, _ = side_curve(64 * world, 64, "cfg2-sized frames, clip grows with N")
         recw["scaling"] = "weak"
         if rank == 0:
@@ -760,7 +811,7 @@ def main() -> None:
         del cw, mmw
 
     # ---- Qwen2-7B: prefill of the interleaved prompt + greedy decode (rank 0; other ranks wait) ----
-    if rank == 0 and world == 1 and not args.no_llm:
+    if args.full and rank == 0 and world == 1 and not args.no_llm:
         from cogstream_amd.llm import Qwen2Engine
         enc.handle._ws.pop("vit", None)  # release the encoder workspace
         torch.cuda.empty_cache()
@@ -883,7 +934,7 @@ def main() -> None:
             del wc, past
 
     # ---- GPU pre-processing of the clip (uint8 frames -> pixel_values) ----
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(5):
@@ -893,7 +944,7 @@ def main() -> None:
                              "host_pil_ms": round(t_host_pre * 1e3, 1), "equal_to_host_path": same_as_host}
 
     # ---- CPU baseline: the oracle on host cores, bounded sample (rank 0, N = 1) ----
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         from oracle import vision as ov
         from cogstream_amd.weights import random_vit_state as rvs
         # the GPU box gives one GPU a 16-core CPU share; more threads than that only thrash

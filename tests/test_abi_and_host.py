@@ -190,7 +190,11 @@ def test_reference_plugin_names_resolve_through_auto_map(tmp_path):
     json.dump({"auto_map": {"AutoModelForCausalLM": "modeling_other.SomethingElse"}}, open(d / "config.json", "w"))
     with pytest.raises(ValueError):
         auto._resolve(str(d), "config.json", "AutoModelForCausalLM", "x.y")
-    ref = "/root/reference/model"
-    if os.path.isdir(ref):      # build container only: the reference's own files name exactly these classes
-        assert auto._resolve(ref, "config.json", "AutoModelForCausalLM", "x.y") is Videollama3Qwen2ForCausalLM
-        assert auto._resolve(ref, "preprocessor_config.json", "AutoProcessor", "x.y") is Videollama3Qwen2Processor
+    # the reference checkpoint's own config files (tests/golden/checkpoint_index.json) name exactly these classes
+    meta = json.load(open(os.path.join(ROOT, "tests", "golden", "checkpoint_index.json")))
+    ref = tmp_path / "ref"
+    ref.mkdir()
+    for n in ("config.json", "preprocessor_config.json"):
+        json.dump(meta[n], open(ref / n, "w"))
+    assert auto._resolve(str(ref), "config.json", "AutoModelForCausalLM", "x.y") is Videollama3Qwen2ForCausalLM
+    assert auto._resolve(str(ref), "preprocessor_config.json", "AutoProcessor", "x.y") is Videollama3Qwen2Processor

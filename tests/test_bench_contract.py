@@ -1,6 +1,7 @@
 """bench.py's contract: the FLOP model behind `roofline.achieved` reproduces SURVEY.md section 8(d)'s per-frame figures
-(CPU), and one tiny run prints ONE JSON line with the keys the driver reads, BASELINE.json's metric, the roofline
-object and (when asked for) the CPU baseline (GPU)."""
+(CPU), one tiny --full run prints ONE JSON line with the keys the driver reads, BASELINE.json's metric, the roofline
+object and (when asked for) the CPU baseline (GPU), and a plain run times exactly --steps steps, carries the headline
+keys only and writes its last step's outputs with --dump-outputs (GPU; the dump format on the CPU)."""
 import json
 import os
 import subprocess
@@ -76,11 +77,67 @@ def test_bench_gpus_n_launches_its_own_ranks_without_touching_the_gpu(monkeypatc
     assert out.out.strip() == '{"metric": "m", "n_gpus": 4}' and "noise from a rank" in out.err
 
 
+def test_dump_outputs_are_a_fixed_float_sample_within_the_size_limit(tmp_path):
+    """--dump-outputs: every row's fp64 sum and the same seeded sample of whole rows in fp32 whatever the values;
+    only float32 / float64 files, 64 MB at most; --steps 0 is refused before anything runs"""
+    import numpy as np
+    import torch
+    import bench
+    mm = torch.randn(14784, 3584, generator=torch.Generator().manual_seed(1)).bfloat16()
+    out = bench.token_outputs(mm)
+    again = bench.token_outputs(torch.zeros_like(mm))
+    assert np.array_equal(out["visual_tokens_row_index"], again["visual_tokens_row_index"])
+    rows = out["visual_tokens_row_index"].astype(np.int64)
+    assert len(rows) == bench.DUMP_ROWS and len(set(rows.tolist())) == len(rows) and rows.max() < mm.shape[0]
+    assert np.array_equal(out["visual_tokens_rows"], mm[torch.from_numpy(rows)].float().numpy())
+    assert np.allclose(out["visual_tokens_row_sum"], mm.double().sum(1).numpy(), rtol=0, atol=1e-9)
+    bench.dump_outputs(str(tmp_path / "d"), out)
+    files = sorted(os.listdir(tmp_path / "d"))
+    assert files == sorted(k + ".npy" for k in out)
+    assert sum(os.path.getsize(tmp_path / "d" / f) for f in files) <= 64 << 20
+    assert {str(np.load(tmp_path / "d" / f).dtype) for f in files} <= {"float32", "float64"}
+    small = bench.token_outputs(mm[:100])
+    assert np.array_equal(small["visual_tokens_row_index"], np.arange(100.0))
+    with pytest.raises(AssertionError):
+        bench.dump_outputs(str(tmp_path / "e"), {"ids": np.arange(3)})
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True,
+                       timeout=300, cwd=ROOT)
+    assert r.returncode == 2 and "--steps" in r.stderr
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_times_the_steps_only_and_dumps_its_outputs(tmp_path):
+    """no --full: exactly --steps timed steps, the headline keys and none of the side measurements, and
+    --dump-outputs writes what the last step returned (per-row sums agree with the sampled rows)"""
+    import numpy as np
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    d = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--frames", "8", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    res = json.loads(lines[0])
+    base = json.load(open(os.path.join(ROOT, "BASELINE.json")))
+    assert res["metric"] == base["metric"] and res["unit"] == "frames/s" and res["higher_is_better"] is True
+    assert res["dtype"] == "bf16" and res["steps"] == 3 and res["warmup"] == 1 and res["n_gpus"] == 1
+    assert abs(res["value"] - 8 / (res["ms_per_step"] / 1e3)) < 0.01 * res["value"]
+    for k in ("roofline", "breakdown_ms", "cfg3", "stages", "shard8", "llm", "pipeline", "preprocess", "cpu_baseline"):
+        assert k not in res, k
+    rows = np.load(d / "visual_tokens_rows.npy")
+    idx = np.load(d / "visual_tokens_row_index.npy").astype(np.int64)
+    sums = np.load(d / "visual_tokens_row_sum.npy")
+    m = res["config"]["visual_tokens"]
+    assert rows.dtype == np.float32 and rows.shape == (m, 3584) and np.array_equal(idx, np.arange(m)) and sums.shape == (m,)
+    assert np.isfinite(rows).all() and np.abs(rows).max() > 0
+    assert np.allclose(rows.astype(np.float64).sum(1), sums, rtol=0, atol=1e-6 * np.abs(rows).sum(1).max())
+
+
 @pytest.mark.gpu
 def test_bench_prints_one_json_line_with_the_contract_keys():
     env = dict(os.environ, PYTHONPATH=ROOT)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--frames", "8", "--steps", "1", "--warmup", "1",
-                        "--no-llm", "--no-cpu"], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+                        "--no-llm", "--no-cpu", "--full"], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1

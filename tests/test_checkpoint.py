@@ -187,19 +187,51 @@ def test_tied_embeddings_load_and_wrong_shapes_fail_by_name(tmp_path):
         r2.check_shapes(ck.expected_tensors(vc, lc))
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/model"), reason="build container only")
-def test_processor_from_pretrained_on_the_reference_directory():
-    """AutoProcessor.from_pretrained equivalent on the reference's own model directory (tokenizer + processor configs
-    are present there; weights are not) -- and the model loader names the missing shards instead of crashing"""
-    import numpy as np
+def _byte_level_bpe_files(d):
+    """vocab.json / merges.txt / added_tokens.json in the checkpoint's layout: a byte-level BPE without merges (one id per
+    byte, the GPT-2 byte -> symbol map), padded to the Qwen2 vocabulary size so that the chat specials and <image> get
+    their real ids. The real vocabulary is reference data and does not ship."""
+    bs = list(range(33, 127)) + list(range(161, 173)) + list(range(174, 256))
+    sym = dict(zip(bs, bs))
+    for n, b in enumerate(b for b in range(256) if b not in sym):
+        sym[b] = 256 + n
+    vocab = {chr(sym[b]): b for b in range(256)}
+    vocab.update({f"<|unused_{i}|>": i for i in range(256, 151643)})
+    added = {"<|endoftext|>": 151643, "<|im_start|>": 151644, "<|im_end|>": 151645, "<image>": 151665}
+    added.update({f"<|reserved_{i}|>": i for i in range(151646, 151665)})
+    with open(os.path.join(d, "vocab.json"), "w", encoding="utf-8") as f:
+        json.dump(vocab, f, ensure_ascii=False)
+    with open(os.path.join(d, "merges.txt"), "w", encoding="utf-8") as f:
+        f.write("#version: 0.2\n")
+    with open(os.path.join(d, "added_tokens.json"), "w", encoding="utf-8") as f:
+        json.dump(added, f)
+
+
+def test_processor_from_pretrained_on_the_reference_directory(meta, tmp_path):
+    """AutoProcessor.from_pretrained equivalent on the reference's model directory, rebuilt from its metadata files
+    (tests/golden/checkpoint_index.json: the configs and model.safetensors.index.json; the weights are not there) -- and
+    the model loader names the missing shards instead of crashing. The real tokenizer comes replayed (tokenizer=); the
+    directory's own vocab.json / merges.txt, loaded by checkpoint.load_tokenizer, are a byte-level stand-in that must
+    see the same prompt text and the same 512 <image> ids."""
     from cogstream_amd import checkpoint as ck
     from cogstream_amd.processing import CogStreamProcessor, synthetic_clip
-    proc = CogStreamProcessor.from_pretrained("/root/reference/model")
+    from replay_tokenizer import ReplayTokenizer
+    d = str(tmp_path)
+    _write_dir(d, meta)
+    with open(os.path.join(d, ck.INDEX), "w") as f:
+        json.dump({"metadata": {"total_size": meta["total_size"]}, "weight_map": meta["weight_map"]}, f)
+    _byte_level_bpe_files(d)
+    replay = ReplayTokenizer()
+    proc = CogStreamProcessor.from_pretrained(d, tokenizer=replay)
     assert (proc.max_tokens, proc.min_tokens, proc.video_merge_size) == (16384, 16, 2)
     frames, ts = synthetic_clip(8, 224, 224)
-    out = proc(conversation=[{"role": "user", "content": [{"type": "video", "video": frames, "timestamps": ts},
-                                                          {"type": "text", "text": "What is happening in the video?"}]}],
-               add_system_prompt=True, add_generation_prompt=True)
+    conv = [{"role": "user", "content": [{"type": "video", "video": frames, "timestamps": ts},
+                                         {"type": "text", "text": "What is happening in the video?"}]}]
+    out = proc(conversation=conv, add_system_prompt=True, add_generation_prompt=True)
     assert out["input_ids"].shape == (1, 621) and int((out["input_ids"] == 151665).sum()) == 512
+    own = CogStreamProcessor.from_pretrained(d)
+    ids = own(conversation=conv, add_system_prompt=True, add_generation_prompt=True)["input_ids"][0]
+    assert int((ids == 151665).sum()) == 512
+    assert own.tokenizer.decode(ids.tolist()) == replay.decode(out["input_ids"][0])
     with pytest.raises(FileNotFoundError, match="git-LFS"):
-        ck.Checkpoint("/root/reference/model")
+        ck.Checkpoint(d)

@@ -292,7 +292,7 @@ def test_two_rank_hip_encoder_equals_single_process(dev, tmp_path):
 
 def test_bench_cfg3_mode_and_extra_key(dev):
     """bench.py --config cfg3 times BASELINE configs[2] (256 frames at 140 x 280); the default run carries it as the
-    extra key `cfg3` beside the cfg2 headline"""
+    extra key `cfg3` beside the cfg2 headline with --full"""
     env = dict(os.environ, PYTHONPATH=ROOT)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "cfg3", "--steps", "2", "--warmup", "1",
                         "--no-llm", "--no-cpu"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
@@ -300,8 +300,8 @@ def test_bench_cfg3_mode_and_extra_key(dev):
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert d["scaling"] == "strong" and d["config"]["frames"] == 256 and d["config"]["patches"] == 51200
     assert "140x280" in d["config"]["workload"] and d["value"] > 0 and "cfg3" not in d
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-llm", "--no-cpu"],
-                       capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-llm", "--no-cpu",
+                        "--full"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert d["config"]["frames"] == 64 and d["scaling"] == "strong" and d["cfg3"]["frames_per_gpu"] == 256 and d["ranks_seen"] == 1

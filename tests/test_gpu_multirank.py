@@ -141,7 +141,7 @@ def test_bench_gpus_2_starts_its_own_ranks(dev):
     processes before it touches the GPU, relays rank 0's JSON line and exits with their status. COGS_BENCH_REHEARSAL=1
     puts both ranks on this box's one GPU (gloo). N > 1 headline: strong scaling of the metric's 64-frame clip."""
     env = dict(ENV, COGS_BENCH_REHEARSAL="1")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full"],
                        capture_output=True, text=True, timeout=1100, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

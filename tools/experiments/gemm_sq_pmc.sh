@@ -9,7 +9,7 @@ for grp in "SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA GRBM_GUI_ACTIVE
            "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_ANY SQ_WAVE_CYCLES" \
            "SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_INSTS_LDS SQ_INSTS_SALU" \
            "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR"; do
-  timeout -k 10 300 rocprofv3 --pmc $grp --kernel-trace --output-format csv -d $O/g$i -- python3 $R/bench.py --steps 1 --warmup 0 --no-llm --no-cpu --no-cfg3 --emulate-shard 0 --vit-streams 1 --no-session > $O/g$i.out 2> $O/g$i.err || echo "group $i failed"
+  timeout -k 10 300 rocprofv3 --pmc $grp --kernel-trace --output-format csv -d $O/g$i -- python3 $R/bench.py --full --steps 1 --warmup 0 --no-llm --no-cpu --no-cfg3 --emulate-shard 0 --vit-streams 1 --no-session > $O/g$i.out 2> $O/g$i.err || echo "group $i failed"
   i=$((i+1))
 done
 python3 - "$O" <<'PY'

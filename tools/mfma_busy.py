@@ -14,7 +14,7 @@ for f in glob.glob(sys.argv[1] + "/**/*counter_collection.csv", recursive=True):
         k = row["Kernel_Name"].replace("(anonymous namespace)::", "").replace("void ", "")[:60]
         a = acc[k][row["Counter_Name"]]
         a[0] += float(row["Counter_Value"]); a[1] += 1
-print("# rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace -- python3 bench.py --steps 1 --warmup 0 --no-llm --no-cpu --no-cfg3")
+print("# rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace -- python3 bench.py --full --steps 1 --warmup 0 --no-llm --no-cpu --no-cfg3")
 print("# kernel | dispatches | elapsed cycles (GUI_ACTIVE/8) | MFMA busy cycles (sum over 1024 SIMDs) | mfma_busy | algorithmic MFMA cycles, useful share (cfg2)")
 M = 59136
 ALGO = {"gemm_tn_pp64_kernel<2057>": 2.0 * M * 4352 * 1152 / 1024,

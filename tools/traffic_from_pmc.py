@@ -21,8 +21,8 @@ def avg(path, counter):
 f, nf = avg(sys.argv[1], "FETCH_SIZE")
 w, nw = avg(sys.argv[2], "WRITE_SIZE")
 print(json.dumps({
-    "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) on `bench.py --steps 1 --warmup 0 --no-llm "
-              f"--no-cpu`, averaged over the {nf} / {nw} gemm_tn_* launches of each pass; FETCH_SIZE doubled per the gfx950 "
+    "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) on `bench.py --full --steps 1 --warmup 0 "
+              f"--no-llm --no-cpu`, averaged over the {nf} / {nw} gemm_tn_* launches of each pass; FETCH_SIZE doubled per the gfx950 "
               "correction (MI355X_MICROARCH.md, HBM)",
     "fetch_kb_per_launch": f, "write_kb_per_launch": w,
     "gemm_hbm_bytes_per_launch": (2.0 * f + w) * 1024.0}, indent=1))
