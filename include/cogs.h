@@ -94,7 +94,11 @@ const char* cogs_debug_list(void);
 /* C[M,N] = epilogue(A[M,K] . W[N,K]^T). nn.Linear / Conv2d(k=s=14) replacement
  * (model/modeling_videollama3_encoder.py:194-210,246-248,275,369-373; cogreasoner_chat.py:179-211).
  * K must be a multiple of 64 (bf16) / 32 (f32) -- pad with zeros; N a multiple of 4;
- * lda/ldw/ldc/ldr in elements, rows 16-byte aligned. bias [N] and residual [M,N] nullable.
+ * lda/ldw/ldc/ldr in elements. A and W rows must be 16-byte aligned (lda / ldw a multiple of 8 bf16 or 4 fp32 elements,
+ * else COGS_E_INVALID). C and residual rows need only the alignment of four elements (ldc / ldr and the C / residual
+ * pointers a multiple of 4 elements: 8 bytes for bf16); rows that are 16-byte aligned take the wide stores, others the
+ * per-wave epilogue, with the same results. residual may alias C (ldr == ldc: in-place x += f(x)).
+ * bias [N] and residual [M,N] nullable.
  * rope: if rope_cos != NULL, columns [0, rope_cols) are rotated with tables [M, head_dim/2] (fp32), or --
  * rope_sin == NULL -- with ONE interleaved table [M, head_dim/2, 2] = (cos, sin) in rope_cos (faster);
  * weight rows must be packed so that columns (2i, 2i+1) of a head are the rotate_half pair
@@ -134,9 +138,13 @@ typedef struct {
      *   A W whose rows do not sum to zero gives wrong results without any error. The rounding of W to bf16 leaves a
      *   row sum s_n != 0, i.e. an error rstd * mean * s_n that grows with |mean / std| of a row of A;
      *   cogstream_amd.weights.fold_layernorm removes it by moving a handful of weights per row one bf16 step so that
-     *   the ROUNDED row sums to zero too (|s_n| < one step of the row's smallest weights). The four specialised
-     *   epilogues that exist: {LNFOLD, LNFOLD + rope, LNFOLD + GELU_TANH} with M >= 2; anything else (M == 1,
-     *   residual / GELU_ERF / SWIGLU / fp32 output together with ln_ab or row_stats) returns COGS_E_UNSUPPORTED. */
+     *   the ROUNDED row sums to zero too (|s_n| < one step of the row's smallest weights). The specialised
+     *   epilogues that exist, all with M >= 2 and bf16 or fp32 inputs:
+     *     row_stats: bias, bias + residual (the out-proj / fc2 form, residual in place included);
+     *     ln_ab:     alone, + rope, + GELU_TANH, + rope + head-major output.
+     *   Anything else together with ln_ab or row_stats returns COGS_E_UNSUPPORTED: M == 1, row_stats without bias, any
+     *   activation with row_stats, residual / GELU_ERF / SWIGLU / fp32 output with ln_ab, fp32 output with row_stats.
+     *   ln_ab with bias, ln_ab without col_c and row_stats with N % 64 != 0 return COGS_E_INVALID. */
     float* row_stats;
     const float* ln_ab;
     const float* col_c;
@@ -145,7 +153,8 @@ typedef struct {
      * column n) is stored at  C[((n / hm_cols) * (hm_cols / head_dim) + (n % hm_cols) / head_dim) * hm_rows * head_dim
      * + m * head_dim + n % head_dim]  -- [block][head][row][head_dim], every head's rows contiguous (ldc is ignored; M <=
      * hm_rows; head_dim % 8 == 0; hm_cols % head_dim == 0; N % hm_cols == 0; hm_rows * hm_cols * 2 < 2^32).
-     * cogs_attn_desc.head_stride reads that layout. 0 = row-major C[m][n]. */
+     * cogs_attn_desc.head_stride reads that layout. 0 = row-major C[m][n]. M == 1 or fp32 inputs return COGS_E_UNSUPPORTED,
+     * an activation, a residual, fp32 output or a violated shape condition COGS_E_INVALID (row_stats: see above). */
     int64_t hm_rows;
     int hm_cols;
 } cogs_gemm_desc;

@@ -22,6 +22,13 @@ def _L():
     return _lib
 
 
+def _assert_body(want, what=""):
+    """the kernel body the last cogs_gemm ran (cogs_debug_get("gemm_last_body"): 1 128x128, 2 256x128 ring, 3 K-tile
+    ping-pong, 4 whole-line ping-pong, 5 ping-pong + ring split, 6 GEMV)"""
+    got = _L().debug_get("gemm_last_body")
+    assert got == want, (what, "ran body", got, "expected", want)
+
+
 @pytest.mark.parametrize("dtype,tol", [(torch.bfloat16, 1.2e-2), (torch.float32, 2e-5)])
 @pytest.mark.parametrize("M,N,K", [(128, 128, 64), (300, 256, 192), (1, 512, 256), (77, 132, 128), (1024, 1152, 1152),
                                    (515, 132, 64), (777, 384, 704)])
@@ -34,6 +41,9 @@ def test_gemm_bias_residual(dev, dtype, tol, M, N, K):
     r = torch.randn(M, N).to(dtype)
     ref = a.float() @ w.float().t() + b.float() + r.float()
     out = ops.gemm(a.to(dev), w.to(dev), b.to(dev), residual=r.to(dev))
+    # M >= 512 on the 256x128 ring: fp32 always; bf16 (1024, 1152, 1152) because the few-tile cost model prices its 19
+    # ping-pong tiles above 36 ring tiles
+    _assert_body(6 if M == 1 else 1 if M < 512 else 2)
     assert out.dtype == dtype
     assert rel_err(out.float(), ref) < tol
 
@@ -65,6 +75,7 @@ def test_gemm_gelu(dev, act):
     pre = a.float() @ w.float().t() + b.float()
     ref = F.gelu(pre, approximate="tanh") if act == "tanh" else F.gelu(pre)
     out = ops.gemm(a.to(dev), w.to(dev), b.to(dev), act=L.ACT_GELU_TANH if act == "tanh" else L.ACT_GELU_ERF)
+    _assert_body(1)
     assert rel_err(out.float(), ref) < 1.2e-2
 
 
@@ -79,6 +90,7 @@ def test_gemm_swiglu(dev, M):
     ref = F.silu(x.float() @ wg.float().t()) * (x.float() @ wu.float().t())
     gu = torch.stack([wg, wu], dim=1).reshape(2 * I, H).contiguous()
     out = ops.gemm(x.to(dev), gu.to(dev), act=L.ACT_SWIGLU)
+    _assert_body(6 if M == 1 else 1)
     assert out.shape == (M, I)
     assert rel_err(out.float(), ref) < 1.2e-2
 
@@ -87,8 +99,9 @@ def test_gemm_swiglu(dev, M):
                                                  (1300, 7, True), (1300, 7, False)])
 def test_gemm_rope_epilogue(dev, M, heads, interleaved):
     """columns [0, rope_cols) rotated as rotate_half pairs after the (d, d+hd/2) row interleave; both table
-    formats; M = 1300 reaches the 256x128 (heads 2) and ping-pong (heads 7) kernels, whose interior wave tiles
-    take the lean epilogue while the tile straddling rope_cols and the ragged last row block take the general one"""
+    formats; M = 1300 reaches the 256x128 ring kernel with both head counts (heads 7: the few-tile cost model prices
+    36 ping-pong tiles above 72 ring tiles), whose interior wave tiles take the lean epilogue while the tile straddling
+    rope_cols and the ragged last row block take the general one"""
     ops = _ops()
     torch.manual_seed(3)
     hd, K = 72, 128
@@ -113,6 +126,7 @@ def test_gemm_rope_epilogue(dev, M, heads, interleaved):
                    rope_cos=(torch.stack([ang.cos(), ang.sin()], -1) if interleaved else ang.cos()).contiguous().to(dev),
                    rope_sin=None if interleaved else ang.sin().contiguous().to(dev),
                    rope_cols=2 * heads * hd, head_dim=hd)
+    _assert_body(6 if M == 1 else 1 if M < 512 else 2)
     refp = ref.clone()
     refp[:, :2 * heads] = ref[:, :2 * heads][:, :, perm]
     assert rel_err(out.float().view(M, 3 * heads, hd), refp) < 1.2e-2
@@ -121,7 +135,9 @@ def test_gemm_rope_epilogue(dev, M, heads, interleaved):
 def test_gemm_rope_position_lut_equals_row_table(dev):
     """the ping-pong GEMM's LDS position LUT (2-D rotary: first half of a head's pairs uses the row's h, second half
     its w) must give bit-identical outputs to the per-row (cos, sin) table built from the same angles -- and both
-    must match the plain reference"""
+    must match the plain reference. The LUT exists in the K-tile body only (gemm_pp64 = 0), and this shape's 36
+    ping-pong tiles go to the ring kernel unless the few-tile split is off (gemm_split = 0)."""
+    from cogstream_amd import _lib as L2
     ops = _ops()
     torch.manual_seed(17)
     hd, heads, K, M = 72, 7, 128, 1500            # N = 1512: ping-pong kernel; ragged last row block; rope straddle
@@ -145,8 +161,11 @@ def test_gemm_rope_position_lut_equals_row_table(dev):
     bp[:2 * heads] = bp[:2 * heads][:, perm]
     args = dict(rope_cos=table.to(dev), rope_sin=None, rope_cols=2 * heads * hd, head_dim=hd)
     xa, wa, ba = x.to(dev), wp.reshape(N, K).contiguous().to(dev), bp.reshape(N).contiguous().to(dev)
-    out_tab = ops.gemm(xa, wa, ba, **args)
-    out_lut = ops.gemm(xa, wa, ba, rope_lut=lut.to(dev), rope_rowpos=rowpos.to(dev), **args)
+    with L2.debug_switch("gemm_pp64", 0), L2.debug_switch("gemm_split", 0):
+        out_tab = ops.gemm(xa, wa, ba, **args)
+        _assert_body(3, "table")
+        out_lut = ops.gemm(xa, wa, ba, rope_lut=lut.to(dev), rope_rowpos=rowpos.to(dev), **args)
+        _assert_body(3, "lut")
     assert torch.equal(out_lut, out_tab)
     y = (x.float() @ w.float().t() + b.float()).view(M, 3 * heads, hd)
     cos = torch.cat([ang.cos(), ang.cos()], -1)[:, None, :]
@@ -818,8 +837,8 @@ def test_gemm_row_stats_and_ln_fold(dev, M):
     """LayerNorm fused around the GEMMs: (1) a residual-stream GEMM (N = hidden) also writes per-row partial sums,
     cogs_ln_finalize turns them into (rstd, -rstd * mean); (2) the consuming GEMM reads x itself with W * diag(gamma)
     (rows centred) and applies rstd_r * acc + c_n -- together LN(x) W^T + bias of nn.LayerNorm + nn.Linear
-    (model/modeling_videollama3_encoder.py:382-391). M = 300 / 1300 / 4096 reach the 128x128, 256x128 + ragged ping-pong
-    and the full ping-pong kernels."""
+    (model/modeling_videollama3_encoder.py:382-391). M = 300 reaches the 128x128 kernel; M = 1300 and 4096 the 256x128
+    ring kernel (the few-tile cost model prices 75 ping-pong tiles at M = 4096 above 144 ring tiles)."""
     ops = _ops()
     torch.manual_seed(M)
     H, N2, eps = 1152, 1472, 1e-6
@@ -832,6 +851,7 @@ def test_gemm_row_stats_and_ln_fold(dev, M):
     y32 = a0.float() @ w0.float().t() + b0.float() + res.float()
     part = torch.zeros(M, H // 64, 2, device=dev)
     x = ops.gemm(a0.to(dev), w0.to(dev), b0.to(dev), residual=res.to(dev), row_stats=part)
+    _assert_body(1 if M < 512 else 2, "producer")
     assert rel_err(x.float(), y32) < 1.2e-2
     xs = x.float().cpu()                                                 # the statistics are those of the STORED rows
     want = torch.stack([xs.view(M, H // 64, 64).sum(-1), (xs ** 2).view(M, H // 64, 64).sum(-1)], -1)
@@ -859,6 +879,7 @@ def test_gemm_row_stats_and_ln_fold(dev, M):
     for act, fn in ((L_ACT_NONE(), lambda t: t), (L_ACT_GELU(), lambda t: F.gelu(t, approximate="tanh"))):
         ref = fn(ln @ w1.float().t() + b1.float())
         out = ops.gemm(x, wf.to(dev), None, act=act, ln_ab=ab, col_c=col_c.to(dev))
+        _assert_body(1 if M < 512 else 2, "consumer")
         unfused = ops.gemm(ln.bfloat16().to(dev), w1.to(dev), b1.to(dev), act=act)
         # every row class -- ordinary mean, |mean / std| ~ 8 and ~ 100 -- is as accurate as the unfused bf16 path: with
         # zero-sum weight rows the product on x equals the product on x - mean, whatever the mean (round 2 allowed the
@@ -906,6 +927,7 @@ def test_ln_fold_through_the_c_abi_as_the_header_states_it(dev):
         return d
 
     assert L.lib.cogs_gemm(L.current_stream(), C.byref(desc(M))) == L.OK
+    _assert_body(2)                     # 1500 rows, N = 640 (padded to 768: more than 12 %): the 256x128 ring kernel
     torch.cuda.synchronize()
     assert rel_err(out.float().cpu(), ref) < 1e-2
     assert L.lib.cogs_gemm(L.current_stream(), C.byref(desc(1))) == L.E_UNSUPPORTED
@@ -961,8 +983,9 @@ def test_gemm_head_major_output_equals_row_major_bit_for_bit(dev, M, heads, fold
     attention kernel streams whole 128-byte lines): the same epilogue arithmetic, only the store address changes -- the
     head-major result must be the row-major result re-arranged, bit for bit. heads = 2 / 7: hm_cols is not a multiple of
     64, so a wave tile straddles q / k / v and every tile takes the general epilogue; heads = 16 (the production width):
-    interior tiles take the lean paired epilogue; M covers the 128x128, 256x128 ring and ping-pong kernels, a ragged last
-    row block, and the round-aligned split (14 824 rows)."""
+    interior tiles take the lean paired epilogue; M covers the 128x128 (96 rows) and 256x128 ring kernels (1300, and 2088
+    by the few-tile cost model), the round-aligned split (6400 rows) and the whole-line kernel (14 824 rows, ragged last
+    row block)."""
     ops = _ops()
     g = torch.Generator(device=dev).manual_seed(M + heads)
     hd, K = 72, 1152 if heads == 16 else 128
@@ -983,7 +1006,10 @@ def test_gemm_head_major_output_equals_row_major_bit_for_bit(dev, M, heads, fold
     else:
         args = dict(a=x, w=rnd(N, K), bias=rnd(N), **kw)
     row = ops.gemm(**args)
+    body = _L().debug_get("gemm_last_body")
     hm = ops.gemm(**args, hm_cols=Hc)
+    _assert_body(body, "head-major")
+    assert body == {96: 1, 1300: 2, 2088: 2, 6400: 5, 14824: 4}[M], body
     torch.cuda.synchronize()
     assert hm.shape == (3, heads, M, hd)
     want = row.view(M, 3, heads, hd).permute(1, 2, 0, 3)
