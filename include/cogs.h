@@ -168,7 +168,9 @@ cogs_status cogs_ln_finalize(cogs_stream stream, const float* row_stats, int row
  * row_lo/row_hi (device int32 [q_len], nullable): eager-reference mode, every query sees all
  * keys and `bias` is added to the logits of keys in [row_lo[q], row_hi[q]) (:257-266).
  * causal: key j visible to query i iff j <= i + q_pos0 (Qwen2; q_pos0 = kv_len - q_len).
- * nsplit > 1 splits the keys over workgroups (decode); ws >= nsplit*q_len*hq*(head_dim+2)*4 bytes. */
+ * nsplit > 1 splits the keys over workgroups (decode); ws >= nsplit*q_len*hq*(head_dim+2)*4 bytes.
+ * O: only rows [0, q_len) x columns [0, hq*head_dim) are written; the columns up to ldo and everything before and after
+ * keep their bits. Keys past kv_len / past the last segment and Q rows past q_len are never given weight. */
 typedef struct {
     int dtype;
     const void* Q; const void* K; const void* V; void* O;

@@ -209,6 +209,7 @@ def test_attention_block_diag_bf16(dev, hd, heads, lens):
     g = qkv.to(dev)
     out = ops.attention(g[:, :H], g[:, H:2 * H], g[:, 2 * H:], hq=heads, hkv=heads, head_dim=hd,
                         cu_seqlens=cu.to(dev), max_seqlen=max(lens))
+    assert _L().debug_get("attn_last_kernel") == 1        # classic softmax: the general kernel, not the ViT one
     assert rel_err(out.float(), ref) < 1.5e-2
 
 
@@ -341,10 +342,12 @@ def test_attention_prescaled_q_causal_gqa(dev, S, pos0):
     ref = _attn_ref(q, k, v, hq, hkv, hd, causal=True, q_pos0=pos0, scale=math.log(2.0))
     out = ops.attention(q.to(dev), k.to(dev), v.to(dev), hq=hq, hkv=hkv, head_dim=hd, causal=True, q_pos0=pos0,
                         q_prescaled=True)
+    assert _L().debug_get("attn_last_kernel") == (1 if S == 1 else 5)     # one row: gqa_pack on the general kernel
     assert rel_err(out.float(), ref) < 1.5e-2
     if S == 1:
         out2 = ops.attention(q.to(dev), k.to(dev), v.to(dev), hq=hq, hkv=hkv, head_dim=hd, causal=True, q_pos0=pos0,
                              nsplit=3 if pos0 < 1000 else 20, q_prescaled=True)
+        assert _L().debug_get("attn_last_kernel") == 4
         assert rel_err(out2.float(), ref) < 1.5e-2
 
 
@@ -373,7 +376,7 @@ def test_decode_attention_kernel_edges(dev, hq, hkv, ctx, nsplit):
 
 
 def test_attention_integer_exact(dev):
-    """layout check: one-hot attention (huge scale) must copy integer V rows exactly"""
+    """layout check: two-hot attention (scale 1, scores 512 against <= 256) must copy integer V rows exactly"""
     ops = _ops()
     hd, n = 128, 192
     torch.manual_seed(0)
@@ -386,6 +389,7 @@ def test_attention_integer_exact(dev):
     v = torch.randint(-8, 9, (n, hd)).float()
     out = ops.attention(q.bfloat16().to(dev), k.bfloat16().to(dev), v.bfloat16().to(dev), hq=1, hkv=1, head_dim=hd,
                         scale=1.0)
+    assert _L().debug_get("attn_last_kernel") == 1
     assert torch.equal(out.float().cpu(), v[tgt])
 
 
@@ -400,10 +404,12 @@ def test_attention_causal_gqa_bf16(dev, S, pos0):
     v = torch.randn(ctx, hkv * hd).bfloat16()
     ref = _attn_ref(q, k, v, hq, hkv, hd, causal=True, q_pos0=pos0)
     out = ops.attention(q.to(dev), k.to(dev), v.to(dev), hq=hq, hkv=hkv, head_dim=hd, causal=True, q_pos0=pos0)
+    assert _L().debug_get("attn_last_kernel") == 1
     assert rel_err(out.float(), ref) < 1.5e-2
     if S == 1:
         out2 = ops.attention(q.to(dev), k.to(dev), v.to(dev), hq=hq, hkv=hkv, head_dim=hd, causal=True, q_pos0=pos0,
                              nsplit=3)
+        assert _L().debug_get("attn_last_kernel") == 1      # classic softmax: the general split path + combine
         assert rel_err(out2.float(), ref) < 1.5e-2
 
 
@@ -421,6 +427,7 @@ def test_attention_eager_global_bias(dev, dtype, tol, rowwise):
     g = qkv.to(dev)
     out = ops.attention(g[:, :H], g[:, H:2 * H], g[:, 2 * H:], hq=heads, hkv=heads, head_dim=hd, row_lo=lo.to(dev),
                         row_hi=hi.to(dev), bias=1.0, force_rowwise=rowwise)
+    assert _L().debug_get("attn_last_kernel") == (7 if dtype == torch.float32 else 1)
     assert rel_err(out.float(), ref) < tol
 
 
