@@ -501,6 +501,7 @@ struct VitRange {
     bool fold = false, use_lut = false, prescale_q = false, head_major = false;
     int maxpos = 0, max_seq = 0, uniform_seq = 0;
     float scale = 1.f;
+    int co_streams = 1;                   // ranges encoded side by side on their own streams (CogsGemm::co_streams)
 
     cogs_status begin();
     cogs_status layer(int l);
@@ -516,7 +517,7 @@ struct VitRange {
 // Not while the per-kernel profiler is on: overlapping launches stretch every bracket, so bench.py's `roofline` and
 // `breakdown_ms` describe the kernels one at a time. cogs_vit_set_streams(h, 1) or the debug switch vit_split_max switch it off.
 
-static cogs_status cogs_project_rows(cogs_handle h, hipStream_t st, const void* tokens, int M, void* out, void* ws);
+static cogs_status cogs_project_rows(cogs_handle h, hipStream_t st, const void* tokens, int M, void* out, void* ws, int co_streams);
 
 // proj_out != NULL: every frame range also runs the projector on its own tokens, on its own stream (cogs_vit_encode_project)
 static cogs_status vit_encode_impl(cogs_handle h, cogs_stream stream, const void* pixel_values, int pix_dtype,
@@ -541,7 +542,7 @@ static cogs_status vit_encode_impl(cogs_handle h, cogs_stream stream, const void
         if (proj_out) {
             int64_t toks = 0;
             for (int v = 0; v < V; ++v) toks += grid_sizes[3 * v] * grid_sizes[3 * v + 1] * grid_sizes[3 * v + 2] / (merge_sizes[v] * merge_sizes[v]);
-            COGS_TRY(cogs_project_rows(h, st, out_tokens, (int)toks, proj_out, proj_ws));
+            COGS_TRY(cogs_project_rows(h, st, out_tokens, (int)toks, proj_out, proj_ws, 1));
         }
         return COGS_OK;
     };
@@ -614,7 +615,7 @@ static cogs_status vit_encode_impl(cogs_handle h, cogs_stream stream, const void
         R[r].st = h->aux_streams[r - 1];
         if (hipStreamWaitEvent(R[r].st, h->ev_fork, 0) != hipSuccess) return COGS_E_HIP;
     }
-    cogs_k_gemm_co_streams(S);
+    for (int r = 0; r < S; ++r) R[r].co_streams = S;
     cogs_status rc = COGS_OK;
     for (int r = 0; r < S && rc == COGS_OK; ++r) rc = R[r].begin();
     for (int l = 0; l < w.layers && rc == COGS_OK; ++l)
@@ -626,9 +627,8 @@ static cogs_status vit_encode_impl(cogs_handle h, cogs_stream stream, const void
         const size_t tes = (size_t)w.hidden * esize(w.dtype), pes2 = (size_t)h->proj.out_dim * esize(h->proj.dtype);
         for (int r = 0; r < S && rc == COGS_OK; ++r)
             rc = cogs_project_rows(h, R[r].st, (const char*)out_tokens + (size_t)tok_begin[r] * tes, (int)(tok_begin[r + 1] - tok_begin[r]),
-                                   (char*)proj_out + (size_t)tok_begin[r] * pes2, (char*)proj_ws + (size_t)tok_begin[r] * pes2);
+                                   (char*)proj_out + (size_t)tok_begin[r] * pes2, (char*)proj_ws + (size_t)tok_begin[r] * pes2, S);
     }
-    cogs_k_gemm_co_streams(1);
     // join unconditionally: the caller's stream must not run ahead of anything queued on the other ones
     for (int r = 1; r < S; ++r)
         if (hipEventRecord(h->ev_joins[r - 1], R[r].st) != hipSuccess || hipStreamWaitEvent(st, h->ev_joins[r - 1], 0) != hipSuccess) return COGS_E_HIP;
@@ -730,7 +730,7 @@ cogs_status VitRange::begin() {
     // patch embed: conv2d k=s=14 == GEMM over the 588-element rows (:202-210)
     { PROF(COGS_PROF_OTHER); COGS_TRY(cogs_k_pack_rows(st, pix_dtype, dt, pixel_values, w.patch_dim, xpad, w.patch_pad, (int)N, w.patch_dim, w.patch_pad)); }
     {
-        CogsGemm g; g.dtype = dt;
+        CogsGemm g; g.dtype = dt; g.co_streams = co_streams;
         g.A = xpad; g.lda = w.patch_pad; g.W = w.patch_w; g.ldw = w.patch_pad; g.C = x; g.ldc = H;
         g.bias = w.patch_b; g.M = (int)N; g.N = H; g.K = w.patch_pad;
         if (fold) g.row_stats = stat_part;
@@ -761,7 +761,7 @@ cogs_status VitRange::layer(int l) {
     if (fold) { PROF(COGS_PROF_NORM); COGS_TRY(cogs_k_ln_finalize(st, stat_part, (int)N, H / 64, H, w.ln_eps, ln_ab)); }
     else { PROF(COGS_PROF_NORM); COGS_TRY(cogs_k_layernorm(st, dt, x, ln, L.ln1_g, L.ln1_b, (int)N, H, w.ln_eps)); }
     {
-        CogsGemm g; g.dtype = dt;
+        CogsGemm g; g.dtype = dt; g.co_streams = co_streams;
         g.A = fold ? x : ln; g.lda = H; g.W = L.qkv_w; g.ldw = H; g.C = qkv; g.ldc = 3 * H;
         g.M = (int)N; g.N = 3 * H; g.K = H;
         if (fold) { g.ln_ab = ln_ab; g.col_c = L.qkv_c; }
@@ -790,7 +790,7 @@ cogs_status VitRange::layer(int l) {
         { PROF(COGS_PROF_ATTN); COGS_TRY(cogs_k_attention(st, a)); }
     }
     {
-        CogsGemm g; g.dtype = dt;
+        CogsGemm g; g.dtype = dt; g.co_streams = co_streams;
         g.A = att; g.lda = H; g.W = L.o_w; g.ldw = H; g.C = x; g.ldc = H;
         g.bias = L.o_b; g.residual = x; g.ldr = H; g.M = (int)N; g.N = H; g.K = H;
         if (fold) g.row_stats = stat_part;
@@ -799,7 +799,7 @@ cogs_status VitRange::layer(int l) {
     if (fold) { PROF(COGS_PROF_NORM); COGS_TRY(cogs_k_ln_finalize(st, stat_part, (int)N, H / 64, H, w.ln_eps, ln_ab)); }
     else { PROF(COGS_PROF_NORM); COGS_TRY(cogs_k_layernorm(st, dt, x, ln, L.ln2_g, L.ln2_b, (int)N, H, w.ln_eps)); }
     {
-        CogsGemm g; g.dtype = dt;
+        CogsGemm g; g.dtype = dt; g.co_streams = co_streams;
         g.A = fold ? x : ln; g.lda = H; g.W = L.fc1_w; g.ldw = H; g.C = big; g.ldc = w.inter_pad;
         g.M = (int)N; g.N = w.inter_pad; g.K = H; g.act = COGS_ACT_GELU_TANH;
         if (fold) { g.ln_ab = ln_ab; g.col_c = L.fc1_c; }
@@ -807,7 +807,7 @@ cogs_status VitRange::layer(int l) {
         { PROF(COGS_PROF_GEMM); COGS_TRY(cogs_k_gemm(st, g)); }
     }
     {
-        CogsGemm g; g.dtype = dt;
+        CogsGemm g; g.dtype = dt; g.co_streams = co_streams;
         g.A = big; g.lda = w.inter_pad; g.W = L.fc2_w; g.ldw = w.inter_pad; g.C = x; g.ldc = H;
         g.bias = L.fc2_b; g.residual = x; g.ldr = H; g.M = (int)N; g.N = H; g.K = w.inter_pad;
         if (fold && l + 1 < w.layers) g.row_stats = stat_part;     // the last layer feeds post_layernorm (own kernel)
@@ -875,18 +875,19 @@ cogs_status cogs_project(cogs_handle h, cogs_stream stream, const void* tokens, 
     if (!h || !h->proj_ok || !tokens || !out || M <= 0) return COGS_E_INVALID;
     const cogs_proj_weights& w = h->proj;
     if (!ws || ws_bytes < (size_t)M * w.out_dim * esize(w.dtype)) return COGS_E_WORKSPACE;
-    return cogs_project_rows(h, (hipStream_t)stream, tokens, M, out, ws);
+    return cogs_project_rows(h, (hipStream_t)stream, tokens, M, out, ws, 1);
 }
 
-// the projector's two GEMMs on M rows (arguments checked by the callers; ws holds M x out_dim elements)
-static cogs_status cogs_project_rows(cogs_handle h, hipStream_t st, const void* tokens, int M, void* out, void* ws) {
+// the projector's two GEMMs on M rows (arguments checked by the callers; ws holds M x out_dim elements); co_streams: streams
+// that run a projector of this size side by side
+static cogs_status cogs_project_rows(cogs_handle h, hipStream_t st, const void* tokens, int M, void* out, void* ws, int co_streams) {
     if (M <= 0) return COGS_OK;
     const cogs_proj_weights& w = h->proj;
-    CogsGemm g; g.dtype = w.dtype;
+    CogsGemm g; g.dtype = w.dtype; g.co_streams = co_streams;
     g.A = tokens; g.lda = w.in_dim; g.W = w.w1; g.ldw = w.in_dim; g.C = ws; g.ldc = w.out_dim;
     g.bias = w.b1; g.M = M; g.N = w.out_dim; g.K = w.in_dim; g.act = COGS_ACT_GELU_ERF;
     { PROF(COGS_PROF_GEMM); COGS_TRY(cogs_k_gemm(st, g)); }
-    CogsGemm g2; g2.dtype = w.dtype;
+    CogsGemm g2; g2.dtype = w.dtype; g2.co_streams = co_streams;
     g2.A = ws; g2.lda = w.out_dim; g2.W = w.w2; g2.ldw = w.out_dim; g2.C = out; g2.ldc = w.out_dim;
     g2.bias = w.b2; g2.M = M; g2.N = w.out_dim; g2.K = w.out_dim;
     { PROF(COGS_PROF_GEMM); COGS_TRY(cogs_k_gemm(st, g2)); }

@@ -26,15 +26,13 @@
 #include "kernels.h"
 #include "gemm_epilogue.h"
 #include "debug.h"
+#include "gemm_plan.h"
 #include <stdlib.h>
 
 namespace {
 
-constexpr int BM = 128;
-constexpr int BN = 128;
 constexpr int ROW_BYTES = 128;               // one tile row of the K slab
 constexpr int TILE_BYTES = BM * ROW_BYTES;   // 16 KiB per operand per buffer
-constexpr int GROUP_M = 8;
 
 template <typename T> struct ElemCfg;
 template <> struct ElemCfg<bf16_t> { static constexpr int BK = 64; };
@@ -192,10 +190,8 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(GemmArgs p) {
 // LDS-DMA prefetch two K slabs ahead that stays in flight ACROSS the barrier: one raw s_barrier per
 // K step, counted s_waitcnt vmcnt(6) (= the 6 pieces of the next slab may still be in flight), all
 // LDS in one array (guide section 5, "Pipelining across barriers"). One workgroup per CU.
-constexpr int BM2 = 256;
 constexpr int SLAB2 = (BM2 + BN) * ROW_BYTES;   // 48 KiB per K slab (A 32 KiB then W 16 KiB)
 constexpr int PIECES2 = SLAB2 / 1024 / 8;       // 6 LDS-DMA pieces per wave per slab
-constexpr int PERSISTENT_WGS = 256;             // one workgroup per CU (MI355X: 256 CUs)
 
 template <typename T, int EPI>
 __global__ __launch_bounds__(512, 2) void gemm_tn_256x128_kernel(GemmArgs p) {
@@ -374,7 +370,6 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_256x128_kernel(GemmArgs p) {
 // per K-tile halves the hand-overs: -3..-6 % on every shape but one (in-run A/B: fc1+GELU 0.588 -> 0.569 ms,
 // out-proj 0.224 -> 0.212, fc2 0.610 -> 0.594, Qwen2 gate/up 3.67 -> 3.45; down-proj unchanged). A 5-slot ring
 // (distance 4) and `buffer_load ... lds` pieces instead of `global_load_lds` were both measured without gain.
-constexpr int BM3 = 256, BN3 = 256;
 constexpr int ROW3 = 64;                          // bytes per LDS row = 32 bf16
 constexpr int SLOT3 = (BM3 + BN3) * ROW3;         // 32 KiB per K-tile
 constexpr int RING3 = 4;                          // ring slots (5 = all 160 KiB of LDS: measured, no gain)
@@ -633,7 +628,6 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_pp_kernel(GemmArgs p) {
 constexpr int ROW4 = 128;                         // bytes per LDS row = 64 bf16 = one line of the operand
 constexpr int UNIT4 = 256 * ROW4;                 // 32 KiB: the A rows or the W rows of one slab
 constexpr int RING4 = 5;
-constexpr int TALL4 = 384;                        // rows of a tall tile (its columns: the <= 128 of the ragged column block)
 
 template <int EPI>
 __global__ __launch_bounds__(512, 2) void gemm_tn_pp64_kernel(GemmArgs p) {
@@ -952,171 +946,152 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_pp64_kernel(GemmArgs p) {
 
 }  // namespace
 
-// kernel launches issued by cogs_k_gemm on this thread (a round-aligned split is two): lets the profiler bracket
+// kernel launches issued by cogs_k_gemm in this process (a round-aligned split is two): lets the profiler bracket
 // report per-KERNEL averages that can be compared with rocprofv3's kernel stats
-static thread_local long g_gemm_launches = 0;
-// how many streams the caller is feeding with GEMMs of this size at the same time (cogs_vit_encode's two-stream mode: 2).
-// Only the few-tile choice below reads it: with a second stream filling the CUs a launch leaves idle, a partly filled
-// round costs its share of the chip, not a whole round.
-static thread_local int g_co_streams = 1;
-void cogs_k_gemm_co_streams(int streams) { g_co_streams = streams < 1 ? 1 : streams; }
-long cogs_k_gemm_launch_count() { return g_gemm_launches; }
+static std::atomic<long> g_gemm_launches{0};
+long cogs_k_gemm_launch_count() { return g_gemm_launches.load(std::memory_order_relaxed); }
 
 int cogs_k_gemv(hipStream_t st, const CogsGemm& g);
 
 namespace {
 
 template <typename T, int EPI>
-void launch_small(hipStream_t st, const GemmArgs& p, int grid) {
+void launch_small(hipStream_t st, const GemmArgs& p, const GemmLaunch& l) {
     const size_t lds = 4 * TILE_BYTES;
     static std::atomic<uint64_t> attr_done{0};
     cogs_ensure_dyn_lds((const void*)gemm_tn_kernel<T, EPI>, (int)lds, attr_done);
-    ++g_gemm_launches;
-    g_cogs_debug.gemm_last_body = 1;
-    hipLaunchKernelGGL((gemm_tn_kernel<T, EPI>), dim3(grid), dim3(256), lds, st, p);
+    hipLaunchKernelGGL((gemm_tn_kernel<T, EPI>), dim3(l.grid), dim3(256), lds, st, p);
 }
 template <typename T, int EPI>
-void launch_big(hipStream_t st, const GemmArgs& p, int grid) {
+void launch_big(hipStream_t st, const GemmArgs& p, const GemmLaunch& l) {
     const size_t lds = 3 * SLAB2;
     static std::atomic<uint64_t> attr_done{0};
     cogs_ensure_dyn_lds((const void*)gemm_tn_256x128_kernel<T, EPI>, (int)lds, attr_done);
-    const int dbg_wgs = (int)g_cogs_debug.gemm_wgs;
-    const int wgs = dbg_wgs <= 0 ? grid : (grid < dbg_wgs ? grid : dbg_wgs);   // 0 = one tile per workgroup
-    ++g_gemm_launches;
-    g_cogs_debug.gemm_last_body = 2;
-    hipLaunchKernelGGL((gemm_tn_256x128_kernel<T, EPI>), dim3(wgs), dim3(512), lds, st, p);
+    hipLaunchKernelGGL((gemm_tn_256x128_kernel<T, EPI>), dim3(l.grid), dim3(512), lds, st, p);
 }
-// debug switch gemm_pp64 = 0 keeps the 32-wide K-tile kernel (A/B runs); default: the whole-line kernel wherever it exists
-// (every epilogue but the rotary LUT one, for which it has no LDS left -- cogs_k_gemm then takes the rotary factors from
-// global memory instead: measured 1 % faster end to end than the LUT epilogue on the old body)
-bool pp64_enabled() { return g_cogs_debug.gemm_pp64 != 0; }
-// Persistent workgroups of the whole-line kernel for `tiles` tiles. 256 = one per CU; debug switch gemm_even_grid = 1: the
-// fewest workgroups (a multiple of 8: the tile walk is XCD-aware) that still finish in ceil(tiles / 256) rounds, so that every
-// workgroup walks the same number of tiles and the CUs the last round would leave idle are free from the start -- for the
-// other stream's kernel, or for the clock.
-int pp64_grid(int tiles) {
-    if (tiles <= PERSISTENT_WGS) return tiles;
-    if (g_cogs_debug.gemm_even_grid == 0) return PERSISTENT_WGS;
-    const int rounds = (tiles + PERSISTENT_WGS - 1) / PERSISTENT_WGS;
-    const int wgs = ((tiles + rounds - 1) / rounds + 7) / 8 * 8;
-    return wgs < PERSISTENT_WGS ? wgs : PERSISTENT_WGS;
-}
-template <int EPI>
-void launch_pp(hipStream_t st, const GemmArgs& p, int grid) {
-    const size_t lds = RING3 * SLOT3 + ((EPI & EPI_ROPE_LUT) ? 28 * 1024 : 0);   // ring (+ rotary LUT, <= 28 KiB)
-    static std::atomic<uint64_t> attr_done{0};
-    cogs_ensure_dyn_lds((const void*)gemm_tn_pp_kernel<EPI>, (int)lds, attr_done);
-    const bool env_trace = g_cogs_debug.gemm_trace != 0;
-    if (env_trace) {
-        static unsigned long long* dbuf = nullptr;
-        if (!dbuf) (void)hipMalloc(&dbuf, 224 * 8);
-        (void)hipMemsetAsync(dbuf, 0, 224 * 8, st);
-        GemmArgs q = p;
-        q.trace = dbuf;
-        const bool env_pp64t = pp64_enabled();
-        bool done64 = false;
-        if constexpr ((EPI & EPI_ROPE_LUT) == 0) {
-            if (env_pp64t && p.K >= 128) {
-                static std::atomic<uint64_t> attr_done64t{0};
-                cogs_ensure_dyn_lds((const void*)gemm_tn_pp64_kernel<EPI>, RING4 * UNIT4, attr_done64t);
-                hipLaunchKernelGGL((gemm_tn_pp64_kernel<EPI>), dim3(grid < PERSISTENT_WGS ? grid : PERSISTENT_WGS), dim3(512), RING4 * UNIT4, st, q);
-                done64 = true;
-            }
-        }
-        if (!done64)
-        hipLaunchKernelGGL((gemm_tn_pp_kernel<EPI>), dim3(grid < PERSISTENT_WGS ? grid : PERSISTENT_WGS), dim3(512), lds, st, q);
-        unsigned long long h[224];
-        (void)hipMemcpyAsync(h, dbuf, sizeof(h), hipMemcpyDeviceToHost, st);
-        (void)hipStreamSynchronize(st);
-        for (int g = 0; g < 2; ++g) {
-            fprintf(stderr, "[gemm trace] EPI=%d M=%d N=%d K=%d group %d:", EPI, p.M, p.N, p.K, g);
-            for (int i = 0; i + 3 < 96 && h[g * 96 + i + 3]; i += 4)
-                fprintf(stderr, " k%llu/e%llu+%llu(+%llu to the next tile's top)", h[g * 96 + i + 1] - h[g * 96 + i], h[g * 96 + i + 2] - h[g * 96 + i + 1],
-                        h[g * 96 + i + 3] - h[g * 96 + i + 2], (i + 4 < 96 && h[g * 96 + i + 4]) ? h[g * 96 + i + 4] - h[g * 96 + i + 3] : 0ull);
-            fprintf(stderr, "\n");
-        }
+// debug switch gemm_trace: the same launch with a stamp buffer, then the per-tile stamps of workgroup 0 on stderr (synchronises)
+template <typename Launch>
+void traced_launch(hipStream_t st, const GemmArgs& p, const GemmLaunch& l, int epi, Launch&& launch) {
+    static unsigned long long* dbuf = nullptr;
+    if (!dbuf) (void)hipMalloc(&dbuf, 224 * 8);
+    (void)hipMemsetAsync(dbuf, 0, 224 * 8, st);
+    GemmArgs q = p;
+    q.trace = dbuf;
+    launch(q);
+    unsigned long long h[224];
+    (void)hipMemcpyAsync(h, dbuf, sizeof(h), hipMemcpyDeviceToHost, st);
+    (void)hipStreamSynchronize(st);
+    for (int g = 0; g < 2; ++g) {
+        fprintf(stderr, "[gemm trace] EPI=%d M=%d N=%d K=%d group %d:", epi, p.M, p.N, p.K, g);
+        for (int i = 0; i + 3 < 96 && h[g * 96 + i + 3]; i += 4)
+            fprintf(stderr, " k%llu/e%llu+%llu(+%llu to the next tile's top)", h[g * 96 + i + 1] - h[g * 96 + i], h[g * 96 + i + 2] - h[g * 96 + i + 1],
+                    h[g * 96 + i + 3] - h[g * 96 + i + 2], (i + 4 < 96 && h[g * 96 + i + 4]) ? h[g * 96 + i + 4] - h[g * 96 + i + 3] : 0ull);
+        fprintf(stderr, "\n");
+    }
 #ifdef COGS_GEMM_KSTAMPS
-        for (int g = 0; g < 2; ++g) {
-            const unsigned long long* o = h + 192 + g * 8;
-            const double kt_n = p.K / 32.0;
-            if (env_pp64t && (EPI & EPI_ROPE_LUT) == 0) {
-                const unsigned long long* q = h + 192 + g * 12;
-                const double sl = kt_n / 2;
-                fprintf(stderr, "[gemm kstamps] group %d per 64-wide slab: L0 %.0f wait %.0f C0 %.0f+%.0f vm %.0f wait %.0f | L1 %.0f wait %.0f C1 %.0f+%.0f vm %.0f wait %.0f\n",
-                        g, q[0] / sl, q[1] / sl, q[2] / sl, q[3] / sl, q[4] / sl, q[5] / sl, q[6] / sl, q[7] / sl, q[8] / sl, q[9] / sl, q[10] / sl, q[11] / sl);
-            }
-            else
-            fprintf(stderr, "[gemm kstamps] group %d per K-tile: L %.0f wait %.0f C %.0f wait %.0f\n",
-                    g, o[0] / kt_n, o[1] / kt_n, o[2] / kt_n, o[3] / kt_n);
+    for (int g = 0; g < 2; ++g) {
+        const unsigned long long* o = h + 192 + g * 8;
+        const double kt_n = p.K / 32.0;
+        if (l.body == 4) {
+            const unsigned long long* q = h + 192 + g * 12;
+            const double sl = kt_n / 2;
+            fprintf(stderr, "[gemm kstamps] group %d per 64-wide slab: L0 %.0f wait %.0f C0 %.0f+%.0f vm %.0f wait %.0f | L1 %.0f wait %.0f C1 %.0f+%.0f vm %.0f wait %.0f\n",
+                    g, q[0] / sl, q[1] / sl, q[2] / sl, q[3] / sl, q[4] / sl, q[5] / sl, q[6] / sl, q[7] / sl, q[8] / sl, q[9] / sl, q[10] / sl, q[11] / sl);
         }
+        else
+        fprintf(stderr, "[gemm kstamps] group %d per K-tile: L %.0f wait %.0f C %.0f wait %.0f\n",
+                g, o[0] / kt_n, o[1] / kt_n, o[2] / kt_n, o[3] / kt_n);
+    }
 #endif
-        return;
-    }
-    ++g_gemm_launches;
-    const bool env_pp64 = pp64_enabled();
-    if constexpr ((EPI & EPI_ROPE_LUT) == 0) {
-        if (env_pp64 && p.K >= 128) {
-            static std::atomic<uint64_t> attr_done64{0};
-            cogs_ensure_dyn_lds((const void*)gemm_tn_pp64_kernel<EPI>, RING4 * UNIT4, attr_done64);
-            g_cogs_debug.gemm_last_body = 4;
-            hipLaunchKernelGGL((gemm_tn_pp64_kernel<EPI>), dim3(pp64_grid(grid)), dim3(512), RING4 * UNIT4, st, p);
-            return;
-        }
-    }
-    g_cogs_debug.gemm_last_body = 3;
-    hipLaunchKernelGGL((gemm_tn_pp_kernel<EPI>), dim3(grid < PERSISTENT_WGS ? grid : PERSISTENT_WGS), dim3(512), lds, st, p);
 }
-void dispatch_pp(hipStream_t st, const GemmArgs& p, int grid, int mask) {
-#define COGS_PP_CASE(E) case E: launch_pp<E>(st, p, grid); break;
+// the ping-pong bodies: 4 the whole-line kernel, 3 the K-tile kernel (the only one with the rotary LUT epilogue)
+template <int EPI>
+void launch_pp(hipStream_t st, const GemmArgs& p, const GemmLaunch& l) {
+    const size_t lds3 = RING3 * SLOT3 + ((EPI & EPI_ROPE_LUT) ? 28 * 1024 : 0);   // ring (+ rotary LUT, <= 28 KiB)
+    auto launch = [&](const GemmArgs& a) {
+        if constexpr ((EPI & EPI_ROPE_LUT) == 0) {
+            if (l.body == 4) {
+                static std::atomic<uint64_t> attr_done64{0};
+                cogs_ensure_dyn_lds((const void*)gemm_tn_pp64_kernel<EPI>, RING4 * UNIT4, attr_done64);
+                hipLaunchKernelGGL((gemm_tn_pp64_kernel<EPI>), dim3(l.grid), dim3(512), RING4 * UNIT4, st, a);
+                return;
+            }
+        }
+        static std::atomic<uint64_t> attr_done{0};
+        cogs_ensure_dyn_lds((const void*)gemm_tn_pp_kernel<EPI>, (int)lds3, attr_done);
+        hipLaunchKernelGGL((gemm_tn_pp_kernel<EPI>), dim3(l.grid), dim3(512), lds3, st, a);
+    };
+    if (g_cogs_debug.gemm_trace != 0) traced_launch(st, p, l, EPI, launch);
+    else launch(p);
+}
+void dispatch_pp(hipStream_t st, const GemmArgs& p, const GemmLaunch& l, int mask) {
+#define COGS_PP_CASE(E) case E: launch_pp<E>(st, p, l); break;
     switch (mask) {
-        COGS_PP_CASE(0)
-        COGS_PP_CASE(EPI_BIAS)
-        COGS_PP_CASE(EPI_RES)
-        COGS_PP_CASE(EPI_BIAS | EPI_RES)
-        COGS_PP_CASE(EPI_BIAS | EPI_ROPE)
+        COGS_EPI_SPECIALISED(COGS_PP_CASE)
         COGS_PP_CASE(EPI_BIAS | EPI_ROPE | EPI_ROPE_LUT)
-        COGS_PP_CASE(EPI_BIAS | EPI_GELU_TANH)
-        COGS_PP_CASE(EPI_BIAS | EPI_GELU_ERF)
-        COGS_PP_CASE(EPI_BIAS | EPI_ROWSTAT)
-        COGS_PP_CASE(EPI_BIAS | EPI_RES | EPI_ROWSTAT)
-        COGS_PP_CASE(EPI_BIAS | EPI_LNFOLD)
-        COGS_PP_CASE(EPI_BIAS | EPI_ROPE | EPI_LNFOLD)
         COGS_PP_CASE(EPI_BIAS | EPI_ROPE | EPI_ROPE_LUT | EPI_LNFOLD)
-        COGS_PP_CASE(EPI_BIAS | EPI_GELU_TANH | EPI_LNFOLD)
-        COGS_PP_CASE(EPI_BIAS | EPI_ROPE | EPI_HM)
-        COGS_PP_CASE(EPI_BIAS | EPI_ROPE | EPI_LNFOLD | EPI_HM)
-        COGS_PP_CASE(EPI_SWIGLU)
-        COGS_PP_CASE(EPI_F32OUT)
         COGS_PP_CASE(EPI_NOSTORE)
-        default: launch_pp<EPI_GENERIC>(st, p, grid); break;
+        default: launch_pp<EPI_GENERIC>(st, p, l); break;
     }
 #undef COGS_PP_CASE
 }
 
 template <typename T>
-void dispatch(hipStream_t st, const GemmArgs& p, int grid, int mask, bool big) {
+void dispatch(hipStream_t st, const GemmArgs& p, const GemmLaunch& l, int mask) {
+    const bool big = l.body == 2;
 #define COGS_EPI_CASE(E) \
-    case E: if (big) launch_big<T, E>(st, p, grid); else launch_small<T, E>(st, p, grid); break;
+    case E: if (big) launch_big<T, E>(st, p, l); else launch_small<T, E>(st, p, l); break;
     switch (mask) {
-        COGS_EPI_CASE(0)
-        COGS_EPI_CASE(EPI_BIAS)
-        COGS_EPI_CASE(EPI_RES)
-        COGS_EPI_CASE(EPI_BIAS | EPI_RES)
-        COGS_EPI_CASE(EPI_BIAS | EPI_ROPE)
-        COGS_EPI_CASE(EPI_BIAS | EPI_GELU_TANH)
-        COGS_EPI_CASE(EPI_BIAS | EPI_GELU_ERF)
-        COGS_EPI_CASE(EPI_BIAS | EPI_ROWSTAT)
-        COGS_EPI_CASE(EPI_BIAS | EPI_RES | EPI_ROWSTAT)
-        COGS_EPI_CASE(EPI_BIAS | EPI_LNFOLD)
-        COGS_EPI_CASE(EPI_BIAS | EPI_ROPE | EPI_LNFOLD)
-        COGS_EPI_CASE(EPI_BIAS | EPI_GELU_TANH | EPI_LNFOLD)
-        COGS_EPI_CASE(EPI_BIAS | EPI_ROPE | EPI_HM)
-        COGS_EPI_CASE(EPI_BIAS | EPI_ROPE | EPI_LNFOLD | EPI_HM)
-        COGS_EPI_CASE(EPI_SWIGLU)
-        COGS_EPI_CASE(EPI_F32OUT)
-        default: if (big) launch_big<T, EPI_GENERIC>(st, p, grid); else launch_small<T, EPI_GENERIC>(st, p, grid); break;
+        COGS_EPI_SPECIALISED(COGS_EPI_CASE)
+        default: if (big) launch_big<T, EPI_GENERIC>(st, p, l); else launch_small<T, EPI_GENERIC>(st, p, l); break;
     }
 #undef COGS_EPI_CASE
+}
+
+// the one place the host code reads the gemm_* switches that decide a plan
+GemmTuning tuning_snapshot() {
+    GemmTuning t;
+    t.gemm_pp64 = g_cogs_debug.gemm_pp64; t.gemm_tall = g_cogs_debug.gemm_tall; t.gemm_even_grid = g_cogs_debug.gemm_even_grid;
+    t.gemm_pingpong = g_cogs_debug.gemm_pingpong; t.gemm_small = g_cogs_debug.gemm_small; t.gemm_wgs = g_cogs_debug.gemm_wgs;
+    t.gemm_pad_pct = g_cogs_debug.gemm_pad_pct; t.gemm_rope_lut = g_cogs_debug.gemm_rope_lut;
+    t.gemm_group_m = g_cogs_debug.gemm_group_m; t.gemm_split = g_cogs_debug.gemm_split;
+    t.gemm_co_streams = g_cogs_debug.gemm_co_streams; t.gemm_ring_cost_permille = g_cogs_debug.gemm_ring_cost_permille;
+    t.gemm_nostore = g_cogs_debug.gemm_nostore;
+    return t;
+}
+
+// one launch of a plan: rows [row0, row0 + l.rows) of g, every row-dependent pointer re-based (rows are independent: same
+// arithmetic per row, same K order, so a row's result does not depend on which launch computed it)
+int launch_rows(hipStream_t st, const CogsGemm& g, const EpiArgs& epi, int mask, const GemmLaunch& l, int row0) {
+    const int es = g.dtype == COGS_DT_BF16 ? 2 : 4;
+    const size_t r0 = (size_t)row0;
+    GemmArgs p;
+    p.trace = nullptr; p.rope_lut = nullptr; p.rope_lut_bytes = 0;
+    p.epi_serial = (int)g_cogs_debug.gemm_epi_serial;
+    p.A = (const char*)g.A + r0 * g.lda * es; p.lda = g.lda * es;
+    p.W = (const char*)g.W; p.ldw = g.ldw * es;
+    p.M = l.rows; p.N = g.N; p.K = g.K;
+    p.nbm = l.nbm; p.nbn = l.nbn; p.group_m = l.group_m; p.cf = l.cf; p.ntiles = l.ntiles;
+    p.epi = epi;
+    p.epi.C += r0 * (g.hm_rows > 0 ? g.head_dim : g.ldc) * (g.out_f32 ? 4 : es);   // head-major: rows advance by head_dim inside every head block
+    if (g.residual) p.epi.R += r0 * g.ldr * es;
+    if (g.rope_rowpos) p.epi.rope_rowpos += r0;
+    if (g.row_stats) p.epi.stat_part += r0 * (g.N / 64) * 2;
+    if (g.ln_ab) p.epi.ln_ab += r0 * 2;
+    if (g.rope_cos) {
+        const size_t per_row = (size_t)(g.head_dim / 2) * (g.rope_sin ? 1 : 2);
+        p.epi.rope_cos += r0 * per_row;
+        if (g.rope_sin) p.epi.rope_sin += r0 * per_row;
+    }
+    if (l.rope_lut) {
+        mask |= EPI_ROPE_LUT;
+        p.rope_lut = g.rope_lut; p.rope_lut_bytes = g.rope_maxpos * (g.head_dim / 4) * 8;
+        p.epi.rope_lut_lds = RING3 * SLOT3;
+    }
+    if (l.body >= 3) dispatch_pp(st, p, l, l.nostore ? EPI_NOSTORE : mask);
+    else if (g.dtype == COGS_DT_BF16) dispatch<bf16_t>(st, p, l, mask);
+    else dispatch<float>(st, p, l, mask);
+    return COGS_LAUNCH_CHECK();
 }
 
 }  // namespace
@@ -1127,154 +1102,35 @@ int cogs_k_gemm(hipStream_t st, const CogsGemm& g) {
     if (g.M <= 0 || g.N <= 0 || g.K <= 0) return COGS_E_INVALID;
     if (g.K % BK != 0 || g.N % 4 != 0) return COGS_E_INVALID;
     if ((g.lda * es) % 16 != 0 || (g.ldw * es) % 16 != 0) return COGS_E_INVALID;
+    const int mask = cogs_epi_mask(g);
     // the fused-LayerNorm features exist in the specialised MFMA epilogues only: the single-row GEMV and the run-time
     // (EPI_GENERIC) epilogue know neither, and silently dropping them would return un-normalised rows
-    if ((g.row_stats || g.ln_ab) && (g.M == 1 || cogs_epi_mask(g) == EPI_GENERIC)) return COGS_E_UNSUPPORTED;
+    if ((g.row_stats || g.ln_ab) && (g.M == 1 || mask == EPI_GENERIC)) return COGS_E_UNSUPPORTED;
     if (g.hm_rows > 0 && (g.M == 1 || g.dtype != COGS_DT_BF16)) return COGS_E_UNSUPPORTED;       // head-major output: bf16 MFMA kernels only
-    if (g.M == 1) { ++g_gemm_launches; g_cogs_debug.gemm_last_body = 6; return cogs_k_gemv(st, g); }
-    if (g.rms_gamma) return COGS_E_UNSUPPORTED;   // fused RMSNorm exists for the single-token GEMV only
-    GemmArgs p;
-    p.trace = nullptr; p.rope_lut = nullptr; p.rope_lut_bytes = 0; p.group_m = GROUP_M;
-    p.epi_serial = (int)g_cogs_debug.gemm_epi_serial;
-    const int rc = cogs_fill_epi(g, &p.epi);
-    if (rc != COGS_OK) return rc;
-    p.A = (const char*)g.A; p.lda = g.lda * es;
-    p.W = (const char*)g.W; p.ldw = g.ldw * es;
-    p.M = g.M; p.N = g.N; p.K = g.K;
-    const bool env_small = g_cogs_debug.gemm_small != 0;
-    const bool env_nopp = g_cogs_debug.gemm_pingpong == 0;
-    const int n_pad = (g.N + BN3 - 1) / BN3 * BN3;
-    const int env_waste = (int)g_cogs_debug.gemm_pad_pct;
-    const bool pp_fits = n_pad * 100 <= g.N * env_waste;   // default: <= 12 % of the MFMAs spent on N padding (N = 1152 -> 1280 measured faster than the 256x128 ring kernel)
-    if (!env_nopp && !env_small && g.dtype == COGS_DT_BF16 && g.M >= 1024 && pp_fits && !g.force_small_tile &&
-        !g.force_mid_tile) {
-        p.nbm = (g.M + BM3 - 1) / BM3;
-        p.nbn = (g.N + BN3 - 1) / BN3;
-        const bool env_nostore = g_cogs_debug.gemm_nostore != 0;
-        const bool env_nolut = g_cogs_debug.gemm_rope_lut == 0;
-        // Tall tiles for a ragged column block of <= 128 columns (whole-line kernel only; see TALL4): p.nbn then counts the
-        // whole column blocks, and a group of the walk must be a whole number of 384-row tiles.
-        const int ragged_cols = g.N % BN3;
-        const bool tall = g_cogs_debug.gemm_tall != 0 && pp64_enabled() && g.K >= 128 && g.N > BN3 && ragged_cols > 0 &&
-                          ragged_cols <= 128;
-        if (tall) p.nbn = g.N / BN3;
-        // tile walk: groups of group_m row blocks x all column blocks. Measured (in-run A/B, cfg2 shapes): few column
-        // blocks with a long K (fc2: 5 x K 4352) want small groups (2: 0.627 -> 0.591 ms), many column blocks with a
-        // short K (fc1: 17 x K 1152) want 8 (2: +7 %)
-        const int env_gm = (int)g_cogs_debug.gemm_group_m;
-        const bool few_cols_long_k = (g.N + BN3 - 1) / BN3 <= 6 && g.K >= 2048;
-        p.group_m = env_gm > 0 ? env_gm : (few_cols_long_k ? 2 : GROUP_M);
-        if (tall) p.group_m = env_gm > 0 ? (env_gm + 2) / 3 * 3 : (few_cols_long_k ? 3 : 6);
-        p.cf = p.group_m * p.nbn + (tall ? p.group_m * BM3 / TALL4 : 0);
-        // tiles of the first `rows` rows (a whole number of row blocks, or all of M)
-        auto count_tiles = [&](int rows) {
-            const int nbm = (rows + BM3 - 1) / BM3;
-            const int full = nbm / p.group_m, last = nbm % p.group_m;
-            int n = full * p.cf + last * p.nbn;
-            if (tall && last) n += (rows - full * p.group_m * BM3 + TALL4 - 1) / TALL4;
-            return n;
-        };
-        // row blocks (with tall tiles: a multiple of three = whole tall tiles) whose tiles number at most `tiles`
-        auto whole_blocks = [&](int tiles) {
-            return tall ? tiles * 3 / (3 * p.nbn + 2) / 3 * 3 : tiles / p.nbn;
-        };
-        int pp_mask = cogs_epi_mask(g);
-        p.rope_lut = nullptr; p.rope_lut_bytes = 0;
-        if ((pp_mask & ~EPI_LNFOLD) == (EPI_BIAS | EPI_ROPE) && g.rope_lut && g.rope_rowpos && !g.rope_sin && !env_nolut && !pp64_enabled()) {
-            const int lut_bytes = g.rope_maxpos * (g.head_dim / 4) * 8;
-            if (lut_bytes > 0 && lut_bytes <= 28 * 1024 && g.rope_maxpos < 65536) {
-                pp_mask |= EPI_ROPE_LUT;
-                p.rope_lut = g.rope_lut; p.rope_lut_bytes = lut_bytes;
-                p.epi.rope_lut_lds = RING3 * SLOT3;
-            }
-        }
-        // Round-aligned split. The persistent kernel walks nbm*nbn tiles with 256 workgroups; when the last round
-        // is mostly empty (N = 1152 at cfg2: 1155 tiles = 4.5 rounds, half the CUs idle for a whole tile time) the
-        // leading row blocks that make up WHOLE rounds stay here and the remaining rows go to the 256x128 kernel,
-        // whose half-size tiles fill the chip again (rows are independent: same arithmetic per row, same K order, so
-        // a row's result does not depend on which kernel computed it).
-        const bool env_nosplit = g_cogs_debug.gemm_split == 0;
-        const int nb = count_tiles(g.M);
-        p.ntiles = nb;
-        const int rounds = nb / PERSISTENT_WGS, rem = nb % PERSISTENT_WGS;
-        int mb_main = -1;      // >= 0: row blocks that stay in this kernel (0 = none: the whole GEMM goes to the ring kernel)
-        // (calibrated on K = 1152 .. 4352, the ViT shapes; longer K -- the Qwen2 prompt pass at M = 2048 -- keeps the
-        // plain ping-pong launch)
-        const int env_co = (int)g_cogs_debug.gemm_co_streams;   // A/B runs
-        const int S = env_co > 0 ? env_co : g_co_streams;
-        if (!env_nosplit && !env_nostore && nb <= 2 * PERSISTENT_WGS && g.K <= 4352) {
-            // Few tiles (one rank's share of a frame-sharded clip: M = 6 400 is 125 tiles for N = 1152 and 350 = 1.37
-            // rounds for QKV): the time is rounds x one tile, so the choice is by rounds. Calibrated on the four ViT
-            // shapes at M = 3 200 .. 14 784 (tools/cal_tiles.sh, rocprofv3; round 4 with the whole-line kernel,
-            // tools/experiments/cring_sweep.sh): a round of 256x128 ring tiles takes 0.72 of a round of ping-pong tiles of
-            // the same K; a second launch costs about 0.08 of one. With a second stream running the other half of the clip
-            // (S = 2) the CUs a launch leaves idle are not lost, so a launch costs max(1, its share of the chip) and is never
-            // split: measured at 3 200 / 3 696 / 6 400 / 14 784 rows per stream, the ring kernel wins the first two (65 and
-            // 75 ping-pong tiles: -2 %, -7 % of the step), the ping-pong kernel the third (125 tiles: -12 %) and the unsplit
-            // launch the last (-4 %).
-            const int rbm = (g.M + BM2 - 1) / BM2, rbn = (g.N + BN - 1) / BN;
-            auto launch_cost = [&](int tiles) {
-                return S == 1 ? (float)((tiles + PERSISTENT_WGS - 1) / PERSISTENT_WGS)
-                              : fmaxf(1.f, (float)S * (float)tiles / (float)PERSISTENT_WGS);
-            };
-            const float c_ring = (float)g_cogs_debug.gemm_ring_cost_permille * 1e-3f;   // 0.72; the switch is for calibration sweeps
-            const float c_launch = 0.08f;
-            const float cost_pp = launch_cost(nb);
-            const float cost_ring = c_ring * launch_cost(rbm * rbn);
-            float best = cost_pp;
-            if (cost_ring < best) { best = cost_ring; mb_main = 0; }
-            if (S == 1 && rounds == 1 && rem > 0) {
-                const int mb = whole_blocks(PERSISTENT_WGS);           // whole row blocks inside the first round
-                const int rows_rem = g.M - mb * BM3;
-                if (mb > 0 && rows_rem >= 512) {     // the remainder must reach the 256x128 ring kernel the cost model prices
-                    const float cost_split = 1.f + c_ring * launch_cost(((rows_rem + BM2 - 1) / BM2) * rbn) + c_launch;
-                    if (cost_split < best) { best = cost_split; mb_main = mb; }
-                }
-            }
-        } else if (S == 1 && !env_nosplit && !env_nostore && g.K >= 2048 && rounds >= 2 && rem > 0 && rem * 100 < PERSISTENT_WGS * 45) {
-            // (many tiles: pays when a tile is long against a second launch and the last round is less than ~45 % full:
-            // measured with the two-segment K loop at K = 1152: -2 %; K = 3584, last round 34 % full: +2 %; K = 18944,
-            // 34 %: +6 %; K = 4352, 51 % full (ViT fc2): -2 %, so it no longer splits)
-            const int mb = whole_blocks(rounds * PERSISTENT_WGS);    // whole row blocks within the full rounds
-            if (mb > 0 && g.M - mb * BM3 >= 512) mb_main = mb;
-        }
-        const bool env_choice = g_cogs_debug.gemm_choice != 0;      // diagnostics: which body each shape gets
-        if (env_choice) fprintf(stderr, "[gemm choice] M=%d N=%d K=%d: %d ping-pong tiles (%d rounds + %d), mb_main %d\n", g.M, g.N, g.K, nb, rounds, rem, mb_main);
-        if (mb_main >= 0) {
-            const int rows_main = mb_main * BM3;
-            CogsGemm b = g;
-            b.M = g.M - rows_main; b.force_mid_tile = 1;
-            b.A = (const char*)g.A + (size_t)rows_main * g.lda * es;
-            b.C = (char*)g.C + (size_t)rows_main * (g.hm_rows > 0 ? g.head_dim : g.ldc) * (g.out_f32 ? 4 : es);   // head-major: rows advance by head_dim inside every head block
-            if (g.residual) b.residual = (const char*)g.residual + (size_t)rows_main * g.ldr * es;
-            if (g.rope_rowpos) b.rope_rowpos = g.rope_rowpos + rows_main;
-            if (g.row_stats) b.row_stats = g.row_stats + (size_t)rows_main * (g.N / 64) * 2;
-            if (g.ln_ab) b.ln_ab = g.ln_ab + (size_t)rows_main * 2;
-            if (g.rope_cos) {
-                const size_t per_row = (size_t)(g.head_dim / 2) * (g.rope_sin ? 1 : 2);
-                b.rope_cos = g.rope_cos + (size_t)rows_main * per_row;
-                if (g.rope_sin) b.rope_sin = g.rope_sin + (size_t)rows_main * per_row;
-            }
-            if (mb_main > 0) {
-                p.M = rows_main; p.nbm = mb_main;
-                p.ntiles = count_tiles(rows_main);
-                dispatch_pp(st, p, p.ntiles, pp_mask);
-                const int rc2 = COGS_LAUNCH_CHECK();
-                if (rc2 != COGS_OK) return rc2;
-            }
-            const int rc3 = cogs_k_gemm(st, b);
-            if (mb_main > 0) g_cogs_debug.gemm_last_body = 5;
-            return rc3;
-        }
-        dispatch_pp(st, p, nb, env_nostore ? EPI_NOSTORE : pp_mask);
-        return COGS_LAUNCH_CHECK();
+    EpiArgs epi;
+    if (g.M > 1) {
+        if (g.rms_gamma) return COGS_E_UNSUPPORTED;   // fused RMSNorm exists for the single-token GEMV only
+        const int rc = cogs_fill_epi(g, &epi);
+        if (rc != COGS_OK) return rc;
     }
-    const bool big = g.M >= 512 && !g.force_small_tile && !env_small;
-    p.nbm = (g.M + (big ? BM2 : BM) - 1) / (big ? BM2 : BM);
-    p.nbn = (g.N + BN - 1) / BN;
-    const int grid = p.nbm * p.nbn;
-    const int mask = cogs_epi_mask(g);
-    if (g.dtype == COGS_DT_BF16) dispatch<bf16_t>(st, p, grid, mask, big);
-    else dispatch<float>(st, p, grid, mask, big);
-    return COGS_LAUNCH_CHECK();
+
+    GemmQuery q;
+    q.bf16 = g.dtype == COGS_DT_BF16;
+    q.M = g.M; q.N = g.N; q.K = g.K;
+    q.epi_mask = mask;
+    q.force_small_tile = g.force_small_tile != 0;
+    q.rope_lut = g.rope_lut && g.rope_rowpos && !g.rope_sin;
+    q.rope_lut_bytes = g.rope_maxpos < 65536 ? g.rope_maxpos * (g.head_dim / 4) * 8 : 0;
+    q.co_streams = g.co_streams;
+    const GemmPlan plan = cogs_plan_gemm(q, tuning_snapshot());
+
+    if (plan.pp_eligible && g_cogs_debug.gemm_choice != 0)      // diagnostics: which body each shape gets
+        fprintf(stderr, "[gemm choice] M=%d N=%d K=%d: %d ping-pong tiles (%d rounds + %d), mb_main %d\n", g.M, g.N, g.K,
+                plan.pp_tiles, plan.pp_rounds, plan.pp_rem, plan.mb_main);
+    g_gemm_launches.fetch_add(plan.rest.body ? 2 : 1, std::memory_order_relaxed);
+    g_cogs_debug.gemm_last_body = plan.body;
+    if (plan.body == 6) return cogs_k_gemv(st, g);
+    const int rc = launch_rows(st, g, epi, mask, plan.main, 0);
+    if (rc != COGS_OK || !plan.rest.body) return rc;
+    return launch_rows(st, g, epi, mask, plan.rest, plan.rows_main);
 }

@@ -25,7 +25,8 @@ struct CogsGemm {
     int rope_cols = 0;
     int head_dim = 0;
     int force_small_tile = 0;                // testing: always use the 128x128 kernel
-    int force_mid_tile = 0;                  // internal: skip the ping-pong kernel (remainder rows of a round-aligned split)
+    int co_streams = 1;                      // streams the caller feeds with GEMMs of this size at the same time (few-tile choice:
+                                             //   the CUs a launch leaves idle are then not lost; cogs_vit_encode's two-stream mode: 2)
     const void* rms_gamma = nullptr;         // M == 1 only: RMS-normalise A on the fly with this weight
     float rms_eps = 0.f;
     // M == 1 only: output columns [kv_col0, kv_col0 + kv_dim) go to kv_k[0..kv_dim), the next kv_dim to kv_v
@@ -48,10 +49,7 @@ struct CogsGemm {
                                              //   (include/cogs.h, cogs_gemm_desc.ln_ab, has the contract)
 };
 int cogs_k_gemm(hipStream_t st, const CogsGemm& g);
-void cogs_k_gemm_co_streams(int streams);   // hint for the few-tile choice: streams fed with GEMMs of this size at once (thread-local)
 // (a, b) = (rstd, -rstd * mean) per row from the EPI_ROWSTAT partials [rows][tiles][2]: ab [rows][2]
-int cogs_k_ln_finalize(hipStream_t st, const float* stat_part, int rows, int tiles, int H, float eps, float* ab);
-// (a, b) = (rstd, -rstd * mean) per row from the EPI_ROWSTAT partials: ab [rows][2]
 int cogs_k_ln_finalize(hipStream_t st, const float* stat_part, int rows, int tiles, int H, float eps, float* ab);
 
 struct CogsAttn {
@@ -80,7 +78,7 @@ struct CogsAttn {
 int cogs_k_attention_vit(hipStream_t st, const struct CogsAttn& a);   // attn_vit.hip: block-diagonal, hd 72, pre-scaled Q
 int cogs_k_attention_decode(hipStream_t st, const struct CogsAttn& a, float* part_o, float* part_ml);   // attn_decode.hip: one query row, hd 128, key-split partials
 int cogs_k_attention(hipStream_t st, const CogsAttn& a);
-long cogs_k_gemm_launch_count();   // kernels launched by cogs_k_gemm so far on this thread
+long cogs_k_gemm_launch_count();   // kernels launched by cogs_k_gemm so far in this process
 
 
 // norms

@@ -68,7 +68,7 @@ def epi_mask(*, bias, res, rope, act, out_f32, stats, ln, hm) -> int:
 @contextlib.contextmanager
 def switches(**kw):
     L = _L()
-    kw.setdefault("gemm_co_streams", 1)        # the few-tile choice reads a per-thread hint that the encoder sets
+    kw.setdefault("gemm_co_streams", 1)        # cogs_gemm always plans for one stream (CogsGemm::co_streams); pinned so that an override left set cannot reroute a cell
     with contextlib.ExitStack() as st:
         for k, v in kw.items():
             st.enter_context(L.debug_switch(k, v))
