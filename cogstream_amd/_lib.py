@@ -159,6 +159,9 @@ SIGNATURES = {
     "cogs_preprocess_frames": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                        c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_size_t]),
     "cogs_argmax": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "cogs_row_lse_workspace_bytes": (c_int, [c_int, c_int, C.POINTER(c_size_t)]),
+    "cogs_row_lse": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                             c_void_p, c_void_p, c_size_t]),
     "cogs_logits_process": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_float, c_void_p, c_int, c_float,
                                     c_void_p]),
     "cogs_topk": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
@@ -176,6 +179,9 @@ SIGNATURES = {
     "cogs_project": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t]),
     "cogs_llm_load": (c_int, [c_void_p, C.POINTER(LlmWeights)]),
     "cogs_llm_workspace_bytes": (c_int, [c_void_p, c_int, c_int, C.POINTER(c_size_t)]),
+    "cogs_lm_score_workspace_bytes": (c_int, [c_void_p, c_int, C.POINTER(c_size_t)]),
+    "cogs_lm_score": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                              c_void_p, c_void_p, c_size_t]),
     "cogs_llm_forward_segments": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_size_t]),
     "cogs_llm_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, C.POINTER(KV), c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_size_t]),

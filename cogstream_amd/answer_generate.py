@@ -31,8 +31,10 @@ from .chat import parse_selection
 
 
 @torch.inference_mode()
-def infer(conversation, model, processor, select=None, if_visual=None, max_new_tokens: int = 1024, **gen_kwargs):
-    """evaluate/answer_generate.py:60-76"""
+def infer(conversation, model, processor, select=None, if_visual=None, max_new_tokens: int = 1024,
+          score_answer: Optional[str] = None, **gen_kwargs):
+    """evaluate/answer_generate.py:60-76 -> (response, selection); with `score_answer` (a ground-truth answer) a third
+    element: model.score_answers' dict for that answer under the same prompt"""
     inputs = processor(conversation=conversation, add_system_prompt=True, add_generation_prompt=True, return_tensors="pt")
     inputs = {k: (v.to(model.device) if isinstance(v, torch.Tensor) and k in ("pixel_values",) else v) for k, v in inputs.items()}
     if "pixel_values" in inputs and model.dtype == torch.bfloat16:
@@ -47,14 +49,24 @@ def infer(conversation, model, processor, select=None, if_visual=None, max_new_t
         model.set_adapter("full_module")
     output_ids, selection = model.generate(**inputs, max_new_tokens=max_new_tokens, **gen_kwargs)
     response = processor.batch_decode(output_ids, skip_special_tokens=True)[0].strip()
+    if score_answer is not None:
+        return response, selection, model.score_answers(**inputs, answers=[score_answer])[0]
     return response, selection
 
 
+def _add_answer_score(record: Dict[str, Any], score: Dict[str, float]) -> None:
+    """--score-answers: log-probability and perplexity of the ground-truth answer under the prompt that was answered"""
+    import math
+    record["answer_logprob"] = score["sum_logprob"]
+    record["answer_ppl"] = math.exp(-score["mean_logprob"]) if score["n_tokens"] else None
+
+
 def run_session(model, processor, segments: Sequence[Dict[str, Any]], system: str = "You are a helpful assistant.",
-                max_new_tokens: int = 1024, **gen_kwargs) -> List[Dict[str, Any]]:
+                max_new_tokens: int = 1024, score_answers: bool = False, **gen_kwargs) -> List[Dict[str, Any]]:
     """segments: [{"video": uint8 [t,H,W,3], "timestamps": [...], "questions": [str, ...],
                    "answers": [str, ...] (optional ground truth), "relevance": [...] (optional)}]
-    -> per-question records with the reference's result keys (:143)."""
+    -> per-question records with the reference's result keys (:143). score_answers: records with a ground-truth answer
+    also get answer_logprob / answer_ppl (off by default: the records are then exactly the reference's)."""
     conversation: List[Dict[str, Any]] = [{"role": "system", "content": system}]
     records: List[Dict[str, Any]] = []
     hist = 0
@@ -66,15 +78,22 @@ def run_session(model, processor, segments: Sequence[Dict[str, Any]], system: st
                     {"type": "text", "text": q}]})
             else:
                 conversation.append({"role": "user", "content": q})
-            out, selection = infer(conversation, model, processor, max_new_tokens=max_new_tokens, **gen_kwargs)
+            gt = seg.get("answers", [None] * len(seg["questions"]))[i]
+            score = None
+            if score_answers and gt is not None:
+                out, selection, score = infer(conversation, model, processor, max_new_tokens=max_new_tokens,
+                                              score_answer=gt, **gen_kwargs)
+            else:
+                out, selection = infer(conversation, model, processor, max_new_tokens=max_new_tokens, **gen_kwargs)
             if hist > 0:
                 vis, idx = parse_selection(selection)
                 relevance = [1 if j in idx else 0 for j in range(hist)]
             else:
                 vis, relevance = True, []
-            gt = seg.get("answers", [None] * len(seg["questions"]))[i]
             records.append({"qa_id": hist, "question": q, "answer": gt, "prediction": out, "predicted_coi": relevance,
                             "predicted_visual": vis, "coi": (seg.get("relevance") or [None] * len(seg["questions"]))[i]})
+            if score is not None:
+                _add_answer_score(records[-1], score)
             hist += 1
             conversation.append({"role": "assistant", "content": out})
     return records
@@ -161,8 +180,10 @@ def _scalar(x):
     return x.item() if hasattr(x, "item") else x
 
 
-def answer_video(model, processor, video_path: str, query_chain, max_new_tokens: int = 1024, **gen_kwargs):
-    """the body of inference()'s loop for one video (:106-148) -> [[record, ...]] (`Data` of the result file)"""
+def answer_video(model, processor, video_path: str, query_chain, max_new_tokens: int = 1024, score_answers: bool = False,
+                 **gen_kwargs):
+    """the body of inference()'s loop for one video (:106-148) -> [[record, ...]] (`Data` of the result file).
+    score_answers: add answer_logprob / answer_ppl of the ground-truth answer to every record"""
     import os
     conversation: List[Dict[str, Any]] = [{"role": "system", "content": "You are a helpful assistant."}]
     segments: Dict[Any, list] = {}
@@ -177,7 +198,12 @@ def answer_video(model, processor, video_path: str, query_chain, max_new_tokens:
             {"type": "text", "text": _scalar(qas[0]["Q"])}]}
         for i, qa in enumerate(qas):
             conversation.append(cov if i == 0 else {"role": "user", "content": _scalar(qa["Q"])})
-            output, selection = infer(conversation, model, processor, max_new_tokens=max_new_tokens, **gen_kwargs)
+            score = None
+            if score_answers:
+                output, selection, score = infer(conversation, model, processor, max_new_tokens=max_new_tokens,
+                                                 score_answer=str(_scalar(qa["A"])), **gen_kwargs)
+            else:
+                output, selection = infer(conversation, model, processor, max_new_tokens=max_new_tokens, **gen_kwargs)
             if hist > 0:
                 vis, idx = parse_selection(selection)
                 relevance = [1 if j in idx else 0 for j in range(hist)]
@@ -186,19 +212,22 @@ def answer_video(model, processor, video_path: str, query_chain, max_new_tokens:
             video_answer.append({"qa_id": hist, "question": _scalar(qa["Q"]), "answer": _scalar(qa["A"]), "prediction": output,
                                  "predicted_coi": relevance, "predicted_visual": vis,
                                  "coi": qa["info"]["relevance"]})      # the file's own value (the reference's [0] undoes the collate)
+            if score is not None:
+                _add_answer_score(video_answer[-1], score)
             hist += 1
             conversation.append({"role": "assistant", "content": output})
     return [video_answer]
 
 
 def inference(model, dataset: VideoDataset, indices: Sequence[int], processor, save_dir: Optional[str],
-              max_new_tokens: int = 1024, **gen_kwargs) -> List[str]:
+              max_new_tokens: int = 1024, score_answers: bool = False, **gen_kwargs) -> List[str]:
     """:102-150 over this rank's videos; save_dir=None: answer but write nothing (non-writing ranks of a sharded run)"""
     import os
     written = []
     for i in indices:
         item = dataset[i]
-        data = answer_video(model, processor, item["video_path"], item["query_chain"], max_new_tokens, **gen_kwargs)
+        data = answer_video(model, processor, item["video_path"], item["query_chain"], max_new_tokens,
+                            score_answers=score_answers, **gen_kwargs)
         if save_dir is not None:
             written.append(save_to_json(os.path.basename(item["video_path"]), data, save_dir))
     return written
@@ -239,6 +268,8 @@ def main(argv=None) -> int:
     ap.add_argument("--spread_events", action="store_true", help="--mode shard: spread the event-summary passes too")
     ap.add_argument("--max_new_tokens", type=int, default=1024)
     ap.add_argument("--greedy", action="store_true", help="do_sample=False instead of the checkpoint's generation config")
+    ap.add_argument("--score-answers", dest="score_answers", action="store_true",
+                    help="add answer_logprob / answer_ppl of the ground-truth answer to every result record")
     args = ap.parse_args(argv)
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -265,7 +296,8 @@ def main(argv=None) -> int:
         indices, save_dir = list(range(len(dataset))), (args.save_dir if rank == 0 else None)
     else:
         indices, save_dir = sampler_indices(len(dataset), rank, world), args.save_dir
-    written = inference(model, dataset, indices, processor, save_dir, args.max_new_tokens, **gen)
+    written = inference(model, dataset, indices, processor, save_dir, args.max_new_tokens,
+                        score_answers=args.score_answers, **gen)
     import sys
     sys.stdout.write(f"rank {rank}/{world} ({args.mode}): {len(indices)} videos answered, {len(written)} result files written\n")
     sys.stdout.flush()          # one write per line: the ranks share the launcher's pipe

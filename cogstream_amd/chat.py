@@ -125,6 +125,17 @@ def parse_selection(selection_module_output: str):
     return if_visual, idx
 
 
+class CausalLMScore:
+    """what CogReasoner.forward returns (the fields of transformers' CausalLMOutputWithPast that a forward pass without
+    autograd can fill, plus the per-token log-probabilities the loss is the mean of)"""
+
+    def __init__(self, loss, logits, token_logprobs, labels):
+        self.loss, self.logits, self.token_logprobs, self.labels = loss, logits, token_logprobs, labels
+
+    def __getitem__(self, key):
+        return getattr(self, key)
+
+
 class _Stage:
     def __init__(self, owner, name):
         self.times, self.name = getattr(owner, "stage_times", None), name
@@ -521,8 +532,9 @@ class CogReasoner:
         keep = torch.cat(keep).to(mm_features.device)
         return mm_features[keep], compression_mask[keep.to(compression_mask.device)]
 
-    def _compress_visual_tokens(self, compression_mask, input_ids, attention_mask):
-        """:449-476 (inference subset). Returns (row index of every kept visual token, input_ids', mask')"""
+    def _compress_visual_tokens(self, compression_mask, input_ids, attention_mask, labels=None):
+        """:449-476 (inference subset). Returns (row index of every kept visual token, input_ids', mask'), and with
+        `labels` a fourth element: the labels compacted by the same text mask (:468-469)"""
         keep = compression_mask.cpu().numpy().astype(bool)
         ids = input_ids.cpu().numpy()
         sel = ids == self.config.image_token_index
@@ -530,17 +542,26 @@ class CogReasoner:
         text_mask[sel] = keep
         new_ids = torch.from_numpy(ids[text_mask])
         new_mask = attention_mask.cpu()[torch.from_numpy(text_mask)] if attention_mask is not None else None
+        if labels is not None:
+            return (torch.from_numpy(np.nonzero(keep)[0]), new_ids, new_mask,
+                    labels.reshape(-1).cpu()[torch.from_numpy(text_mask)])
         return torch.from_numpy(np.nonzero(keep)[0]), new_ids, new_mask
 
     # ------------------------------------------------------------------ multimodal assembly
     def prepare_inputs_labels_for_multimodal(self, input_ids=None, attention_mask=None, pixel_values=None,
                                              grid_sizes=None, merge_sizes=None, modals=None, total_image_num=0,
-                                             if_visual=True, video_keys=None, position_ids=None):
-        """:513-584 -> (inputs_embeds [1,S',H] on the device, attention_mask [1,S'])"""
+                                             if_visual=True, video_keys=None, position_ids=None, labels=None):
+        """:513-584 -> (inputs_embeds [1,S',H] on the device, attention_mask [1,S']); with `labels` [1,S] a third element:
+        the labels [1,S'] compacted together with the ids through token compression (:540-541,562-564,579-580)"""
         B, N = input_ids.shape
         assert B == 1, "Token compression is only supported for batch_size=1"
         ids = input_ids.reshape(-1).cpu()
         am = attention_mask.reshape(-1) if attention_mask is not None else None
+        want_labels = labels is not None
+        if want_labels:
+            labels = labels.reshape(-1).cpu()
+            assert labels.numel() == N, (labels.numel(), N)
+        none = (None, None, None) if want_labels else (None, None)
         mm = None
         if if_visual:
             pixel_values = pixel_values.to(self.device)
@@ -554,13 +575,15 @@ class CogReasoner:
             assert mm.shape[0] % total_image_num == 0, f"{mm.shape[0]} % {total_image_num} != 0"
             frame_indices = self.select_events_based_on_summary(mm, total_image_num, self.all_timestamps)
             if self._is_helper():       # frame-sharded run: this rank's part (encode, gather, event passes) is done
-                return None, None
+                return none
             mm = self.compress_unimportant_events(mm, mm.shape[0] // total_image_num, frame_indices)
             mask = self._get_compression_mask(pixel_values, batched, grid_sizes, merge_sizes, modals,
                                               minor_frame_indices=frame_indices)
             mm, mask = self._maybe_truncate_visual_tokens(mm, mask, batched, modals, ids, position_ids)      # :555-562
             self.last_debug.update(minor_frames=frame_indices, compression_mask=mask)
-            if self.use_token_compression:
+            if self.use_token_compression and want_labels:
+                rows, ids, am, labels = self._compress_visual_tokens(mask, ids, am, labels)
+            elif self.use_token_compression:
                 rows, ids, am = self._compress_visual_tokens(mask, ids, am)
             else:
                 rows = torch.arange(mm.shape[0])
@@ -570,19 +593,25 @@ class CogReasoner:
             idx[sel] = -(rows.to(torch.int64) + 1)
         else:
             if self._is_helper():
-                return None, None
+                return none
             idx = ids.to(torch.int64)
         embeds = ops.gather_rows(self.llm.packed.embed, mm, idx.to(self.device))
         self.last_debug.update(input_ids=ids)
+        if want_labels:
+            return embeds.unsqueeze(0), (am.reshape(1, -1) if am is not None else None), labels.reshape(1, -1)
         return embeds.unsqueeze(0), (am.reshape(1, -1) if am is not None else None)
 
     # ------------------------------------------------------------------ text side
-    def prepare_inputs(self, selection_module_output: str, original_text: Optional[str] = None):
-        """:478-511 (inference branch) -> (tokenized new prompt, if_visual)"""
+    def prepare_inputs(self, selection_module_output: str, original_text: Optional[str] = None, answer: Optional[str] = None):
+        """:478-511 -> (tokenized new prompt, if_visual); with `answer` (:504-508, the scoring / training branch) ->
+        (tokenized new prompt + answer, number of prompt tokens)"""
         if_visual, sel = parse_selection(selection_module_output)
         hist_qs = [self.hist_qs[i] for i in sel if i < len(self.hist_qs)]
         hist_as = [self.hist_as[i] for i in sel if i < len(self.hist_qs)]  # sic: bound by len(hist_qs) (:502)
         prompt = process_input_ids(original_text, if_visual, hist_qs, hist_as, self.current_question, self.tokenizer)
+        if answer is not None:
+            n_prompt = len(self.tokenizer(prompt, padding=False, truncation=True, return_tensors="pt")["input_ids"][0])
+            return self.tokenizer(prompt + answer, padding=False, truncation=True, return_tensors="pt"), n_prompt
         return self.tokenizer(prompt, padding=False, return_tensors="pt"), if_visual
 
     def generate_language_module(self, input_ids=None, attention_mask=None, max_new_tokens: int = 50,
@@ -667,3 +696,131 @@ class CogReasoner:
         if self._shard is not None:
             self._bcast(list(new))
         return torch.tensor(new, dtype=torch.int64).unsqueeze(0), selection_module_output
+
+    # ------------------------------------------------------------------ teacher-forced scoring
+    @torch.no_grad()
+    def forward(self, input_ids=None, attention_mask=None, labels=None, pixel_values=None, grid_sizes=None,
+                merge_sizes=None, modals=None, num_logits_to_keep: int = 0, total_image_num=None, if_visual=True,
+                video_keys=None, **unused) -> Optional[CausalLMScore]:
+        """:696-751 -- model(**inputs, labels=...) -> .loss / .logits / .token_logprobs / .labels, batch size 1.
+        Semantics of Qwen2ForCausalLM.forward + ForCausalLMLoss: the labels are shifted inside (row i is scored against
+        labels[i + 1]), -100 is ignored, .loss is the mean negative log-probability over the scored positions (fp32
+        scalar tensor; nan when there are none, like torch's cross_entropy; None without labels). .labels are the labels
+        after token compression, .token_logprobs fp32 [1, S'] holds log p(labels[j] | rows before j) at position j (0
+        where ignored and at position 0). The loss comes from cogs_lm_score and never needs the logits.
+        .logits fp32 [1, k, vocab] holds the last `num_logits_to_keep` rows with transformers' meaning of 0 = ALL rows:
+        that is S' x vocab x 4 bytes (2.5 GB for 4 096 tokens at vocab 152 064) -- pass 1 (the next-token row) unless the
+        whole matrix is really wanted. With pixel values `total_image_num` is needed as in generate() (the reference's
+        plain forward omits it and divides by zero, :524,549). Forward pass only: no autograd graph is built, .loss has
+        no grad_fn."""
+        if input_ids.shape[0] != 1:
+            raise NotImplementedError("batched forward (B > 1) is not supported")
+        lab = None
+        if pixel_values is not None and input_ids.shape[1] != 1:
+            got = self.prepare_inputs_labels_for_multimodal(
+                input_ids=input_ids, attention_mask=attention_mask, pixel_values=pixel_values, grid_sizes=grid_sizes,
+                merge_sizes=merge_sizes, modals=modals, total_image_num=total_image_num, if_visual=if_visual,
+                video_keys=video_keys, labels=labels)
+            embeds = got[0]
+            if labels is not None:
+                lab = got[2]
+        else:
+            embeds = None if self._is_helper() else self.llm.embed_tokens(input_ids.reshape(-1)).unsqueeze(0)
+            lab = labels.reshape(1, -1).cpu() if labels is not None else None
+        if self._is_helper():     # frame-sharded run: the llm_rank scores; loss, log-probabilities and labels arrive by broadcast
+            loss, lp, lab_l = self._bcast(None)
+            return CausalLMScore(None if loss is None else torch.tensor(loss, dtype=torch.float32), None,
+                                 None if lp is None else torch.tensor(lp, dtype=torch.float32).reshape(1, -1),
+                                 None if lab_l is None else torch.tensor(lab_l, dtype=torch.int64).reshape(1, -1))
+        embeds = embeds[0]
+        S = embeds.shape[0]
+        hidden = self.llm.forward(embeds, None, want_hidden=True, want_logits=False)["hidden"]
+        loss = token_lp = None
+        if lab is not None:
+            assert lab.shape[1] == S, (lab.shape, S)
+            targets = torch.full((S,), -100, dtype=torch.int64)
+            targets[:-1] = lab[0, 1:]
+            sc = self.llm.score_hidden(hidden, targets)
+            scored = (targets != -100).to(self.device)
+            loss = -(sc["logprobs"].sum() / scored.sum())        # 0 / 0 = nan when nothing is scored, as torch
+            token_lp = torch.zeros(1, S, device=self.device, dtype=torch.float32)
+            token_lp[0, 1:] = sc["logprobs"][:-1]
+        k = int(num_logits_to_keep)
+        logits = self.llm.logits(hidden[-k:] if k > 0 else hidden).unsqueeze(0)
+        if self._shard is not None:
+            self._bcast((None if loss is None else float(loss), None if token_lp is None else token_lp[0].tolist(),
+                         None if lab is None else lab[0].tolist()))
+        return CausalLMScore(loss, logits, token_lp, lab)
+
+    __call__ = forward
+
+    def forward_train(self, input_ids=None, attention_mask=None, num_logits_to_keep: int = 0, pixel_values=None,
+                      grid_sizes=None, merge_sizes=None, modals=None, tokenizer=None, hist_qs=None, hist_as=None,
+                      current_question=None, all_timestamps=None, total_image_num=None, answer=None, cor=None,
+                      if_visual=True, original_text=None, video_keys=None, **unused) -> Optional[CausalLMScore]:
+        """:604-693 -- the reference's training forward as a SCORING pass: the loss of the ground-truth `answer` given the
+        clip, the history turns `cor` selects and the question. Builds the selection string from `cor` (:641-645),
+        prompt + answer through prepare_inputs(answer=) (:646), labels = -100 on the prompt + the answer ids (:649-657,
+        with the reference's length assertion :655), then forward(). `input_ids` / `attention_mask` are accepted and
+        unused, as in the reference (it only takes their device). Forward pass only, under no_grad: this is not a
+        training step -- there are no gradients and nothing to call .backward() on."""
+        self.tokenizer, self.hist_qs, self.hist_as = tokenizer, hist_qs, hist_as
+        self.current_question = current_question
+        self.all_timestamps = torch.tensor(all_timestamps)
+        selection = "[" + ",".join(["yes" if if_visual else "no"] + [str(n) for n in cor]) + "]"
+        new_inputs, n_prompt = self.prepare_inputs(selection, answer=answer, original_text=original_text)
+        new_ids, new_mask = new_inputs["input_ids"], new_inputs["attention_mask"]
+        ans = self.tokenizer(answer, padding=False, truncation=True, return_tensors="pt")["input_ids"]
+        answer_ids = ans[0].tolist() if ans.numel() > 0 else []
+        assert new_ids.shape[1] == n_prompt + len(answer_ids), (new_ids.shape[1], n_prompt, len(answer_ids))
+        labels = torch.tensor([-100] * n_prompt + answer_ids, dtype=torch.int64).unsqueeze(0)
+        self.last_debug.update(train_input_ids=new_ids[0].clone(), train_prompt_tokens=n_prompt)
+        return self.forward(input_ids=new_ids, attention_mask=new_mask, labels=labels, pixel_values=pixel_values,
+                            grid_sizes=grid_sizes, merge_sizes=merge_sizes, modals=modals,
+                            num_logits_to_keep=num_logits_to_keep, total_image_num=total_image_num, if_visual=if_visual,
+                            video_keys=video_keys)
+
+    @torch.no_grad()
+    def score_answers(self, pixel_values=None, grid_sizes=None, merge_sizes=None, modals=None, new_input_ids=None,
+                      new_attention_mask=None, selection_module_output="", if_visual=True, video_keys=None,
+                      answers: Sequence[str] = (), tokenizer=None, **kwargs) -> List[Dict[str, float]]:
+        """generate()'s inputs (what qa_selection returns) + candidate answers -> one dict(sum_logprob, mean_logprob,
+        n_tokens) per candidate: log p(answer tokens | clip, selected history, question). The multimodal prompt is
+        encoded and prefilled ONCE (all rows but its last); every candidate is then scored against that KV cache as
+        [last prompt row, answer tokens but the last] -> answer tokens. Multiple-choice video QA ranks by these numbers;
+        exp(-mean_logprob) is the perplexity of a ground-truth answer. A candidate is a string (tokenized with
+        `tokenizer`, default the one qa_selection was given) or a sequence / tensor of token ids. An empty candidate
+        scores 0 over 0 tokens (mean nan). In a frame-sharded run helper ranks take part in the encode and receive the result by broadcast."""
+        total_image_num = kwargs.pop("total_image_num", None)
+        tok = tokenizer or self.tokenizer
+        helper = self._is_helper()
+        if pixel_values is not None:
+            embeds, _ = self.prepare_inputs_labels_for_multimodal(
+                input_ids=new_input_ids, attention_mask=new_attention_mask, pixel_values=pixel_values,
+                grid_sizes=grid_sizes, merge_sizes=merge_sizes, modals=modals, total_image_num=total_image_num,
+                if_visual=if_visual, video_keys=video_keys)
+            embeds = None if helper else embeds[0]
+        elif not helper:
+            embeds = self.llm.embed_tokens(new_input_ids.reshape(-1))
+        if helper:
+            return self._bcast(None)
+        cand = [tok(a, padding=False, truncation=True, return_tensors="pt")["input_ids"].reshape(-1).to(torch.int64)
+                if isinstance(a, str) else torch.as_tensor(a, dtype=torch.int64).reshape(-1).cpu() for a in answers]
+        S = embeds.shape[0]
+        longest = max([int(c.numel()) for c in cand] + [1])
+        cache = self.llm.new_cache(S + longest)
+        if S > 1:
+            self.llm.forward(embeds[:S - 1], cache, want_logits=False, want_hidden=True)
+        out = []
+        for ids in cand:
+            n = int(ids.numel())
+            if n == 0:
+                out.append({"sum_logprob": 0.0, "mean_logprob": float("nan"), "n_tokens": 0})
+                continue
+            cache.reset(S - 1)
+            rows = embeds[S - 1:] if n == 1 else torch.cat([embeds[S - 1:], self.llm.embed_tokens(ids[:-1])], dim=0)
+            total = float(self.llm.score(rows, ids, cache=cache)["logprobs"].sum())
+            out.append({"sum_logprob": total, "mean_logprob": total / n, "n_tokens": n})
+        if self._shard is not None:
+            self._bcast(out)
+        return out

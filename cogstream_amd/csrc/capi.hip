@@ -153,7 +153,8 @@ const char* cogs_status_string(cogs_status s) {
     }
 }
 
-const char* cogs_version(void) { return "cogstream_amd 0.2 (gfx950)"; }     // 0.2: cogs_gemm_desc.hm_rows / hm_cols, cogs_attn_desc.head_stride
+// 0.2: cogs_gemm_desc.hm_rows / hm_cols, cogs_attn_desc.head_stride; 0.3: cogs_lm_score, cogs_row_lse
+const char* cogs_version(void) { return "cogstream_amd 0.3 (gfx950)"; }
 
 // ---------------------------------------------------------------- diagnostics (csrc/debug.h)
 // accepted range of a switch: on / off unless listed here
@@ -163,6 +164,7 @@ static bool cogs_debug_value_ok(const char* name, int64_t v) {
         {"gemm_wgs", 0, 256}, {"gemm_pad_pct", 100, 400}, {"gemm_group_m", 0, 64}, {"gemm_co_streams", 0, 8},
         {"gemm_ring_cost_permille", 1, 4000}, {"gemv_small_n", 0, 1 << 30}, {"attn_vit", 0, 2}, {"attn_uniform_hint", 0, 1 << 20}, {"attn_prio", 0, 2},
         {"attn_nq", 0, 2}, {"vit_split_max", 0, INT64_MAX}, {"llm_split_keys", 0, 1 << 24}, {"km_row_groups", 0, 1 << 16},
+        {"lm_score_rows", 1, 1 << 16}, {"lm_score_cols", 0, 1 << 24}, {"lm_score_split", 0, 4096},
     };
     for (const Range& r : ranges)
         if (strcmp(name, r.name) == 0) return v >= r.lo && v <= r.hi;
@@ -189,6 +191,10 @@ cogs_status cogs_debug_get(const char* name, int64_t* value) {
     if (strcmp(name, "gemm_last_body") == 0) { *value = g_cogs_debug.gemm_last_body; return COGS_OK; }
     if (strcmp(name, "attn_last_kernel") == 0) { *value = g_cogs_debug.attn_last_kernel; return COGS_OK; }
     if (strcmp(name, "attn_vit_last_end") == 0) { *value = g_cogs_debug.attn_vit_last_end; return COGS_OK; }
+    if (strcmp(name, "lm_score_last_split") == 0) { *value = g_cogs_debug.lm_score_last_split; return COGS_OK; }
+    if (strcmp(name, "lm_score_last_chunk") == 0) { *value = g_cogs_debug.lm_score_last_chunk; return COGS_OK; }
+    if (strcmp(name, "lm_score_last_rows") == 0) { *value = g_cogs_debug.lm_score_last_rows; return COGS_OK; }
+    if (strcmp(name, "lm_score_last_cols") == 0) { *value = g_cogs_debug.lm_score_last_cols; return COGS_OK; }
     return COGS_E_INVALID;
 }
 
@@ -202,7 +208,10 @@ const char* cogs_debug_list(void) {
         "attn_last_kernel (read only): kernel of the last cogs_attention -- 1 general MFMA, 2 ViT unpipelined, 3 ViT pipelined, "
         "4 single-token decode, 5 prompt LDS-DMA, 7 row-wise fp32, 8 ViT pipelined on head-major K/V\n"
         "attn_vit_last_end (read only): ragged end of the last pipelined ViT attention launch -- 10 x tiles behind the four-tile loop + "
-        "32-key blocks of the last tile (41 .. 72: compile-time shape), 0 the run-time form\n";
+        "32-key blocks of the last tile (41 .. 72: compile-time shape), 0 the run-time form\n"
+        "lm_score_last_split / lm_score_last_chunk / lm_score_last_rows / lm_score_last_cols (read only): the last cogs_lm_score / "
+        "cogs_row_lse -- workgroups per row of a full panel in the fold kernel (1: no column split), columns per workgroup, rows and "
+        "columns of a panel\n";
 }
 
 cogs_status cogs_create(int device, cogs_handle* out) {
@@ -411,6 +420,51 @@ cogs_status cogs_logits_process(cogs_stream stream, float* logits, int n, const 
     return cogs_k_logits_process((hipStream_t)stream, logits, n, prev, n_prev, repetition_penalty, allowed, n_allowed,
                                  temperature, tmp);
 }
+
+// workspace of a log-sum-exp walk: per-row state, column-split partials, and (cogs_lm_score) the logits panel
+static size_t lse_carve(const CogsLsePlan& p, bool with_panel, Carver& c, void** state, void** part, float** panel) {
+    *state = c.take(p.state_bytes);
+    *part = p.part_bytes ? c.take(p.part_bytes) : nullptr;
+    *panel = with_panel ? (float*)c.take(p.panel_bytes) : nullptr;
+    return c.off;
+}
+static void lse_report(const CogsLsePlan& p) {
+    g_cogs_debug.lm_score_last_split = p.nsplit;
+    g_cogs_debug.lm_score_last_chunk = p.chunk;
+    g_cogs_debug.lm_score_last_rows = p.rows_b;
+    g_cogs_debug.lm_score_last_cols = p.cols_p;
+}
+
+cogs_status cogs_row_lse_workspace_bytes(int rows, int n, size_t* bytes) {
+    if (rows <= 0 || n <= 0 || !bytes) return COGS_E_INVALID;
+    CogsLsePlan p; cogs_k_lse_plan(rows, n, &p);
+    Carver c(nullptr, 0);
+    void *a, *b; float* pn;
+    *bytes = lse_carve(p, false, c, &a, &b, &pn);
+    return COGS_OK;
+}
+cogs_status cogs_row_lse(cogs_stream stream, const float* logits, int rows, int n, int64_t ld, const int64_t* targets,
+                         float* lse, float* target_logit, int64_t* argmax, float* max_logit, int32_t* n_bad, void* ws,
+                         size_t ws_bytes) {
+    if (!logits || rows <= 0 || n <= 0 || (n & 3) || ld < n || (ld & 3) || ((uintptr_t)logits & 15)) return COGS_E_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    CogsLsePlan p; cogs_k_lse_plan(rows, n, &p);
+    Carver c(ws, ws_bytes);
+    void *state, *part; float* pn;
+    const size_t need = lse_carve(p, false, c, &state, &part, &pn);
+    if (!ws || ws_bytes < need) return COGS_E_WORKSPACE;
+    lse_report(p);
+    for (int r0 = 0; r0 < rows; r0 += p.rows_b) {
+        const int rb = rows - r0 < p.rows_b ? rows - r0 : p.rows_b;
+        for (int c0 = 0; c0 < n; c0 += p.cols_p) {
+            const int wd = n - c0 < p.cols_p ? n - c0 : p.cols_p;
+            COGS_TRY(cogs_k_lse_fold(st, p, logits + (size_t)r0 * ld + c0, ld, rb, wd, c0, targets ? targets + r0 : nullptr,
+                                     target_logit ? target_logit + r0 : nullptr, (char*)state + (size_t)r0 * 16, part));
+        }
+    }
+    return cogs_k_lse_final(st, state, rows, n, targets, lse, target_logit, argmax, max_logit, n_bad);
+}
+
 size_t cogs_sample_workspace_bytes(void) { return cogs_k_sample_ws(); }
 cogs_status cogs_sample(cogs_stream stream, const float* logits, int n, float temperature, int top_k, double top_p,
                         const float* draws,
@@ -1109,6 +1163,49 @@ static cogs_status llm_forward_impl(cogs_handle h, cogs_stream stream, const voi
 cogs_status cogs_llm_forward(cogs_handle h, cogs_stream stream, const void* embeds, int S, cogs_kv* kv,
                              float* last_logits, float* pooled_mean, void* hidden_out, void* ws, size_t ws_bytes) {
     return llm_forward_impl(h, stream, embeds, S, kv, last_logits, pooled_mean, hidden_out, ws, ws_bytes, nullptr, 0, nullptr);
+}
+
+cogs_status cogs_lm_score_workspace_bytes(cogs_handle h, int S, size_t* bytes) {
+    if (!h || !h->llm_ok || !bytes || S <= 0) return COGS_E_INVALID;
+    CogsLsePlan p; cogs_k_lse_plan(S, h->llm.vocab, &p);
+    Carver c(nullptr, 0);
+    void *a, *b; float* pn;
+    *bytes = lse_carve(p, true, c, &a, &b, &pn);
+    return COGS_OK;
+}
+
+// row blocks x vocabulary panels: lm_head GEMM with fp32 output into the panel (the accumulators last_logits comes from),
+// fold into the per-row state, next panel; one last kernel for the outputs. Everything on the caller's stream.
+cogs_status cogs_lm_score(cogs_handle h, cogs_stream stream, const void* hidden, int S, const int64_t* targets, float* lse,
+                          float* target_logit, int64_t* argmax, float* max_logit, int32_t* n_bad, void* ws,
+                          size_t ws_bytes) {
+    if (!h || !h->llm_ok || !hidden || S <= 0) return COGS_E_INVALID;
+    const cogs_llm_weights& w = h->llm;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t es = esize(w.dtype);
+    const int H = w.hidden, V = w.vocab;
+    CogsLsePlan p; cogs_k_lse_plan(S, V, &p);
+    Carver c(ws, ws_bytes);
+    void *state, *part; float* panel;
+    const size_t need = lse_carve(p, true, c, &state, &part, &panel);
+    if (!ws || ws_bytes < need) return COGS_E_WORKSPACE;
+    lse_report(p);
+    for (int r0 = 0; r0 < S; r0 += p.rows_b) {
+        const int rb = S - r0 < p.rows_b ? S - r0 : p.rows_b;
+        for (int c0 = 0; c0 < V; c0 += p.cols_p) {
+            const int wd = V - c0 < p.cols_p ? V - c0 : p.cols_p;
+            CogsGemm g; g.dtype = w.dtype;
+            g.A = (const char*)hidden + (size_t)r0 * H * es; g.lda = H;
+            g.W = (const char*)w.lm_head + (size_t)c0 * H * es; g.ldw = H;
+            g.C = panel; g.ldc = p.cols_p; g.M = rb; g.N = wd; g.K = H; g.out_f32 = 1;
+            { PROF(COGS_PROF_GEMM); COGS_TRY(cogs_k_gemm(st, g)); }
+            { PROF(COGS_PROF_OTHER);
+              COGS_TRY(cogs_k_lse_fold(st, p, panel, p.cols_p, rb, wd, c0, targets ? targets + r0 : nullptr,
+                                       target_logit ? target_logit + r0 : nullptr, (char*)state + (size_t)r0 * 16, part)); }
+        }
+    }
+    PROF(COGS_PROF_OTHER);
+    return cogs_k_lse_final(st, state, S, V, targets, lse, target_logit, argmax, max_logit, n_bad);
 }
 
 cogs_status cogs_llm_forward_segments(cogs_handle h, cogs_stream stream, const void* embeds, int S,

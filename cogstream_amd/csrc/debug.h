@@ -48,7 +48,11 @@
     /* ---- encoder / LLM drivers (csrc/capi.hip), k-means ---- */                                                          \
     X(vit_split_max, 1099511627776LL, "clips above this many patches are encoded on one stream")                           \
     X(llm_split_keys, 0, "> 0: keys per split of the decode attention (0: chosen from the context)")                        \
-    X(km_row_groups, 0, "> 0: row groups of the k-means distance pass (0: sized to fill the chip)")
+    X(km_row_groups, 0, "> 0: row groups of the k-means distance pass (0: sized to fill the chip)")                       \
+    /* ---- teacher-forced scoring (csrc/lm_score.hip) ---- */                                                              \
+    X(lm_score_rows, 2048, "cogs_lm_score / cogs_row_lse: rows of a logits panel")                                          \
+    X(lm_score_cols, 0, "> 0: columns of a logits panel, rounded down to 32 (0: what a 64 MiB panel holds; never more than that)") \
+    X(lm_score_split, 0, "> 0: workgroups per panel row of the fold kernel (0: about 1024 workgroups while a panel has < 512 rows, else 1)")
 
 struct CogsDebug {
 #define COGS_DBG_FIELD(name, dflt, doc) std::atomic<long long> name{dflt};
@@ -63,5 +67,11 @@ struct CogsDebug {
     std::atomic<long long> attn_last_kernel{0};
     // ... and which ragged end the last pipelined ViT launch had: 10 R + blocks of the last tile (41 .. 72), 0 = the run-time form
     std::atomic<long long> attn_vit_last_end{0};
+    // ... and how the last cogs_lm_score / cogs_row_lse walked its logits: workgroups per row of a full panel (1 = no column
+    // split) and the columns each of them folds, and the panel shape
+    std::atomic<long long> lm_score_last_split{0};
+    std::atomic<long long> lm_score_last_chunk{0};
+    std::atomic<long long> lm_score_last_rows{0};
+    std::atomic<long long> lm_score_last_cols{0};
 };
 extern CogsDebug g_cogs_debug;     // capi.hip

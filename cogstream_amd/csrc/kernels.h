@@ -156,3 +156,18 @@ size_t cogs_k_sample_ws();
 int cogs_k_sample(hipStream_t st, const float* logits, int n, float temperature, int top_k, double top_p, const float* draws, uint64_t seed,
                   uint64_t offset, int64_t* out_token, int32_t* kept_idx, float* kept_prob, int* n_kept, int kept_cap,
                   void* ws);
+
+// teacher-forced scoring (lm_score.hip): a [rows, n] fp32 logits matrix is walked as rows_b x cols_p panels; every panel is
+// folded into 16 bytes of per-row state (maximum, sum of exp, first-maximum column); the last call writes the outputs
+struct CogsLsePlan {
+    int rows_b, cols_p;      // panel shape (rows_b * cols_p * 4 <= 64 MiB)
+    int chunk, nsplit;       // columns per workgroup of the fold, workgroups per row of a full panel
+    size_t state_bytes, part_bytes, panel_bytes;
+};
+void cogs_k_lse_plan(int rows, int n, CogsLsePlan* p);
+// panel: fp32 [rows <= rows_b][ld] holding vocabulary columns [col0, col0 + width); col0 == 0 starts a row's state afresh.
+// targets / target_logit / state: already offset to the panel's first row; part: rows_b * nsplit * 16 bytes (nsplit > 1)
+int cogs_k_lse_fold(hipStream_t st, const CogsLsePlan& p, const float* panel, long ld, int rows, int width, int col0,
+                    const int64_t* targets, float* target_logit, void* state, void* part);
+int cogs_k_lse_final(hipStream_t st, const void* state, int rows, int n, const int64_t* targets, float* lse,
+                     float* target_logit, int64_t* argmax, float* max_logit, int* n_bad);

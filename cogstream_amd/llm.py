@@ -114,6 +114,57 @@ class Qwen2Engine:
             out["hidden"] = hidden
         return out
 
+    def score(self, embeds: torch.Tensor, target_ids: torch.Tensor, *, cache: Optional[KVCache] = None) -> Dict[str, torch.Tensor]:
+        """Teacher-forced scoring of S rows: how probable is target_ids[i], the token that FOLLOWS row i (the caller has
+        shifted; -100 = ignore, e.g. on a last row without successor). -> dict(logprobs fp32 [S] (0 where ignored), lse
+        fp32 [S], argmax int64 [S] = the greedy token after every row), on the device. One forward for the final hidden
+        states, then cogs_lm_score: the [S, vocab] logits are never materialised (one panel of at most 64 MiB is).
+        With `cache` the rows sit at positions cache.len ..: prefill a prompt once, then score several continuations
+        against it with cache.reset(prompt_len) in between. Raises ValueError for a target outside the vocabulary
+        (checked once, after everything has been queued). Forward pass only: nothing here is differentiable."""
+        S = embeds.shape[0]
+        target_ids = target_ids.reshape(-1).to(self.device, torch.int64).contiguous()
+        if target_ids.numel() != S:
+            raise ValueError(f"{target_ids.numel()} targets for {S} rows")
+        hidden = self.forward(embeds, cache, want_hidden=True, want_logits=False)["hidden"]
+        return self.score_hidden(hidden, target_ids)
+
+    def score_hidden(self, hidden: torch.Tensor, target_ids: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """score() behind the forward: final-norm hidden states [S, H] + shifted targets -> dict(logprobs, lse, argmax)"""
+        target_ids = target_ids.reshape(-1).to(self.device, torch.int64).contiguous()
+        res = self.lm_score(hidden, target_ids)
+        # the one place the log-probability is formed
+        logprobs = torch.where(target_ids == -100, torch.zeros_like(res["lse"]), res["target_logit"] - res["lse"])
+        n_bad = int(res["n_bad"].item())
+        if n_bad:
+            raise ValueError(f"{n_bad} target ids outside [0, {self.cfg.vocab_size}) (and not -100)")
+        return {"logprobs": logprobs, "lse": res["lse"], "argmax": res["argmax"]}
+
+    def lm_score(self, hidden: torch.Tensor, target_ids: Optional[torch.Tensor]) -> Dict[str, torch.Tensor]:
+        """cogs_lm_score on final-norm hidden states [S, H] -> dict(lse, target_logit, max_logit fp32 [S], argmax int64
+        [S], n_bad int32 [1]); no host synchronisation"""
+        self._activate()
+        hidden = hidden.contiguous()
+        assert hidden.dtype == self.dtype and hidden.shape[1] == self.cfg.hidden_size
+        S = hidden.shape[0]
+        nbytes = C.c_size_t()
+        L.check(L.lib.cogs_lm_score_workspace_bytes(self.handle.h, S, C.byref(nbytes)), "cogs_lm_score_workspace_bytes")
+        ws = self.handle.workspace("lm_score", nbytes.value)
+        f32 = dict(device=self.device, dtype=torch.float32)
+        res = {"lse": torch.empty(S, **f32), "target_logit": torch.empty(S, **f32), "max_logit": torch.empty(S, **f32),
+               "argmax": torch.empty(S, device=self.device, dtype=torch.int64),
+               "n_bad": torch.empty(1, device=self.device, dtype=torch.int32)}
+        L.check(L.lib.cogs_lm_score(self.handle.h, L.current_stream(), hidden.data_ptr(), S, L.ptr(target_ids),
+                                    L.ptr(res["lse"]), L.ptr(res["target_logit"]), L.ptr(res["argmax"]),
+                                    L.ptr(res["max_logit"]), L.ptr(res["n_bad"]), ws.data_ptr(), ws.numel()), "cogs_lm_score")
+        return res
+
+    def logits(self, hidden_rows: torch.Tensor) -> torch.Tensor:
+        """lm_head on a caller-chosen SMALL set of final-norm hidden rows [R, H] -> fp32 [R, vocab] (cogs_gemm with fp32
+        output, the accumulators of forward()'s last-row logits): R * vocab * 4 bytes, 0.6 MB per row at vocab 152 064"""
+        self._activate()
+        return ops.gemm(hidden_rows.contiguous(), self.packed.lm_head, out_f32=True)
+
     def forward_segments(self, embeds: torch.Tensor, seg_lens: Sequence[int]) -> torch.Tensor:
         """several independent sequences stored back to back -> mean of the final hidden states of each, fp32
         [nseg, H] (cogs_llm_forward_segments): one var-len prefill instead of one forward per sequence"""

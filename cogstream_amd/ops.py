@@ -309,6 +309,33 @@ def argmax(logits: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Te
     return out
 
 
+def row_lse(logits: torch.Tensor, targets: Optional[torch.Tensor] = None, *, out: Optional[dict] = None) -> dict:
+    """cogs_row_lse on fp32 logits [rows, n] (unit column stride; the row stride may exceed n) -> dict(lse, target_logit,
+    max_logit fp32 [rows], argmax int64 [rows], n_bad int32 [1]), all on the device. targets: int64 [rows], -100 = ignored
+    row; a target outside [0, n) is ignored too and counted in n_bad (the caller decides when to look). The
+    log-probability of a row's target is target_logit - lse. out: preallocated tensors under the same keys."""
+    _need_cuda(logits, targets)
+    assert logits.dim() == 2 and logits.dtype == torch.float32 and logits.stride(1) == 1
+    rows, n = logits.shape
+    res = dict(out or {})
+    for key, dt in (("lse", torch.float32), ("target_logit", torch.float32), ("max_logit", torch.float32),
+                    ("argmax", torch.int64)):
+        if key not in res:
+            res[key] = torch.empty(rows, device=logits.device, dtype=dt)
+        assert res[key].dtype == dt and res[key].numel() == rows and res[key].is_contiguous()
+    if "n_bad" not in res:
+        res["n_bad"] = torch.empty(1, device=logits.device, dtype=torch.int32)
+    if targets is not None:
+        assert targets.dtype == torch.int64 and targets.numel() == rows and targets.is_contiguous()
+    nbytes = C.c_size_t()
+    check(L.lib.cogs_row_lse_workspace_bytes(rows, n, C.byref(nbytes)), "cogs_row_lse_workspace_bytes")
+    ws = torch.empty(nbytes.value, device=logits.device, dtype=torch.uint8)
+    check(L.lib.cogs_row_lse(current_stream(), ptr(logits), rows, n, logits.stride(0) if rows > 1 else max(n, logits.stride(0)),
+                             ptr(targets), ptr(res["lse"]), ptr(res["target_logit"]), ptr(res["argmax"]),
+                             ptr(res["max_logit"]), ptr(res["n_bad"]), ptr(ws), ws.numel()), "cogs_row_lse")
+    return res
+
+
 def logits_process(logits: torch.Tensor, prev: Optional[torch.Tensor], repetition_penalty: float = 1.0,
                    allowed: Optional[torch.Tensor] = None, temperature: float = 1.0) -> None:
     """in place on a fp32 [vocab] row"""

@@ -89,7 +89,8 @@ const char* cogs_debug_list(void);
 /* DESCRIPTORS (cogs_gemm_desc, cogs_attn_desc, ...) MUST BE ZERO-INITIALISED before the caller fills in what it uses
  * (`cogs_gemm_desc d = {0};` / memset / ctypes' default constructor): they carry no size or version member, new optional
  * fields are appended at the end with 0 = "off" (round 5: cogs_gemm_desc.hm_rows / hm_cols, cogs_attn_desc.head_stride), and a
- * field left holding stack garbage switches a feature on. cogs_version() names the ABI revision: "0.2" added those three. */
+ * field left holding stack garbage switches a feature on. cogs_version() names the ABI revision: "0.2" added those three,
+ * "0.3" cogs_lm_score / cogs_row_lse (new entry points only; every older signature is unchanged). */
 
 /* C[M,N] = epilogue(A[M,K] . W[N,K]^T). nn.Linear / Conv2d(k=s=14) replacement
  * (model/modeling_videollama3_encoder.py:194-210,246-248,275,369-373; cogreasoner_chat.py:179-211).
@@ -313,6 +314,20 @@ cogs_status cogs_topk(cogs_stream stream, const float* logits, int n, int top_k,
  * trip; else device float [n] holding the CPU generator's exponential draws of this step (parity with the
  * reference's CPU sampler). Optional kept_idx/kept_prob [kept_cap] + n_kept report the surviving ids and their
  * renormalised probabilities (any order). ws >= cogs_sample_workspace_bytes(). */
+/* Per-row log-sum-exp, target logit and first-maximum argmax of fp32 logits [rows, n] (row stride ld elements; n and ld
+ * multiples of 4, `logits` 16-byte aligned): what F.cross_entropy(logits, targets, ignore_index=-100, reduction="none")
+ * and logits.argmax(-1) read out of the logits of Qwen2ForCausalLM.forward (behind model/cogreasoner_chat.py:680-693,
+ * 737-751); the log-probability of row r's target is target_logit[r] - lse[r]. targets (device int64 [rows], nullable):
+ * -100 = ignored row; a target outside [0, n) cannot be refused without a synchronisation, so such a row is treated as
+ * ignored and counted in *n_bad (device int32, nullable; set by the call). Outputs, each nullable: lse fp32 [rows] = log
+ * sum_v exp(logit_v); target_logit fp32 [rows] (0 on ignored rows); argmax int64 [rows] (FIRST maximum, as torch.argmax /
+ * cogs_argmax); max_logit fp32 [rows]. The matrix is walked in the panels cogs_lm_score uses (cogs_debug_get
+ * "lm_score_last_rows" / "_cols" / "_split" / "_chunk" report them), every element read once; no floating-point atomics: the same
+ * call gives the same bits. Workspace: 16 bytes per row + the column-split partials of one panel. */
+cogs_status cogs_row_lse_workspace_bytes(int rows, int n, size_t* bytes);
+cogs_status cogs_row_lse(cogs_stream stream, const float* logits, int rows, int n, int64_t ld, const int64_t* targets,
+                         float* lse, float* target_logit, int64_t* argmax, float* max_logit, int32_t* n_bad, void* ws,
+                         size_t ws_bytes);
 size_t cogs_sample_workspace_bytes(void);
 cogs_status cogs_sample(cogs_stream stream, const float* logits, int n, float temperature, int top_k, double top_p,
                         const float* draws,
@@ -424,6 +439,22 @@ cogs_status cogs_llm_workspace_bytes(cogs_handle h, int max_tokens, int max_cont
 cogs_status cogs_llm_forward(cogs_handle h, cogs_stream stream, const void* embeds, int S, cogs_kv* kv,
                              float* last_logits, float* pooled_mean, void* hidden_out, void* ws,
                              size_t ws_bytes);
+
+/* Teacher-forced scoring: the outputs of cogs_row_lse for logits = lm_head(hidden) WITHOUT the [S, vocab] logits --
+ * Qwen2ForCausalLM.forward(labels=) / ForCausalLMLoss behind forward_train and forward (model/cogreasoner_chat.py:604-693,
+ * 696-751), which materialise them (2.5 GB of fp32 for 4 096 tokens at vocab 152 064). hidden [S, hidden] in the weights'
+ * dtype = cogs_llm_forward's hidden_out (with or without a KV cache); targets[i] = the token that FOLLOWS row i (the
+ * caller shifts; -100 = ignore, out of range = ignored and counted in *n_bad); lse / target_logit / argmax / max_logit /
+ * n_bad as for cogs_row_lse. The library walks row blocks x vocabulary panels: the lm_head GEMM writes one fp32 panel
+ * (the accumulators last_logits comes from, not rounded to bf16), a fold kernel reduces it into 16 bytes of state per
+ * row, the next panel overwrites it. cogs_lm_score_workspace_bytes does not grow with S * vocab: one panel of at most
+ * 64 MiB (so that it stays in the 256 MiB Infinity Cache between the GEMM that writes it and the fold that reads it) +
+ * 16 bytes per row + the partials of a column-split fold. S == 1 takes the GEMV of last_logits and gives cogs_argmax's
+ * token for the same row. COGS_E_INVALID: S <= 0 or no LLM loaded; COGS_E_WORKSPACE: ws too small. */
+cogs_status cogs_lm_score_workspace_bytes(cogs_handle h, int S, size_t* bytes);
+cogs_status cogs_lm_score(cogs_handle h, cogs_stream stream, const void* hidden, int S, const int64_t* targets,
+                          float* lse, float* target_logit, int64_t* argmax, float* max_logit, int32_t* n_bad,
+                          void* ws, size_t ws_bytes);
 
 /* nseg independent sequences stored back to back in embeds [S,H] (cu_seqlens_host [nseg+1], host memory, 0 .. S):
  * one stateless forward -- positions and causal attention restart at every sequence -- and the mean over each
