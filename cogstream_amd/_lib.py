@@ -112,6 +112,36 @@ class LlmWeights(C.Structure):
     ]
 
 
+class GemvFp8Desc(C.Structure):
+    _fields_ = [
+        ("dtype", c_int),
+        ("x", c_void_p),
+        ("W", c_void_p), ("ldw", c_int64),
+        ("scale", c_void_p),
+        ("C", c_void_p),
+        ("bias", c_void_p),
+        ("residual", c_void_p),
+        ("N", c_int), ("K", c_int),
+        ("act", c_int),
+        ("out_f32", c_int),
+        ("rope_cos", c_void_p),
+        ("rope_sin", c_void_p),
+        ("rope_cols", c_int),
+        ("head_dim", c_int),
+        ("q_scale", c_float), ("q_cols", c_int),
+        ("rms_gamma", c_void_p), ("rms_eps", c_float),
+        ("kv_k", c_void_p), ("kv_v", c_void_p), ("kv_col0", c_int), ("kv_dim", c_int),
+    ]
+
+
+class LlmFp8Layer(C.Structure):
+    _fields_ = [(n, c_void_p) for n in ("qkv_q", "o_q", "gu_q", "down_q", "qkv_s", "o_s", "gu_s", "down_s")]
+
+
+class LlmFp8Weights(C.Structure):
+    _fields_ = [("layers", c_int), ("lm_head_q", c_void_p), ("lm_head_s", c_void_p), ("layer", C.POINTER(LlmFp8Layer))]
+
+
 class KV(C.Structure):
     _fields_ = [("k", c_void_p), ("v", c_void_p), ("max_len", c_int), ("len", c_int)]
 
@@ -129,6 +159,10 @@ SIGNATURES = {
     "cogs_profile_begin": (c_int, [c_void_p]),
     "cogs_profile_end": (c_int, [c_void_p, c_void_p, C.POINTER(c_float), C.POINTER(c_int)]),
     "cogs_gemm": (c_int, [c_void_p, C.POINTER(GemmDesc)]),
+    "cogs_gemv_fp8": (c_int, [c_void_p, C.POINTER(GemvFp8Desc)]),
+    "cogs_quantize_fp8_rows": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p,
+                                       c_int64]),
+    "cogs_llm_attach_fp8": (c_int, [c_void_p, C.POINTER(LlmFp8Weights)]),
     "cogs_ln_finalize": (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),
     "cogs_attention": (c_int, [c_void_p, C.POINTER(AttnDesc)]),
     "cogs_layernorm": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float]),

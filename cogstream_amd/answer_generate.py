@@ -270,6 +270,8 @@ def main(argv=None) -> int:
     ap.add_argument("--greedy", action="store_true", help="do_sample=False instead of the checkpoint's generation config")
     ap.add_argument("--score-answers", dest="score_answers", action="store_true",
                     help="add answer_logprob / answer_ppl of the ground-truth answer to every result record")
+    ap.add_argument("--decode-weights", dest="decode_weights", choices=["bf16", "fp8"], default="bf16",
+                    help="fp8: W8A16 decode -- the token loop streams e4m3 codes of the Qwen2 linears (half the weight bytes)")
     args = ap.parse_args(argv)
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -279,7 +281,8 @@ def main(argv=None) -> int:
     shard = args.mode == "shard" and world > 1
     model = AutoModelForCausalLM.from_pretrained(args.model_path, trust_remote_code=True, torch_dtype=torch.bfloat16,
                                                  attn_implementation="flash_attention_2", device=dev,
-                                                 load_llm=not shard or rank == 0 or args.spread_events)
+                                                 load_llm=not shard or rank == 0 or args.spread_events,
+                                                 decode_weights=None if args.decode_weights == "bf16" else args.decode_weights)
     processor = AutoProcessor.from_pretrained(args.model_path, trust_remote_code=True, device=dev)
     if model.llm is not None:
         if args.lora_adapter_1_path:

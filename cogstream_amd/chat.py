@@ -180,7 +180,8 @@ class CogReasoner:
     # ------------------------------------------------------------------ loading
     @classmethod
     def from_pretrained(cls, path: str, torch_dtype=None, device=None, attn_implementation: str = "flash_attention_2",
-                        trust_remote_code: bool = True, load_llm: bool = True, **unused) -> "CogReasoner":
+                        trust_remote_code: bool = True, load_llm: bool = True, decode_weights: Optional[str] = None,
+                        **unused) -> "CogReasoner":
         """AutoModelForCausalLM.from_pretrained(model_path, trust_remote_code=True, torch_dtype=torch.bfloat16,
         attn_implementation="flash_attention_2") of evaluate/answer_generate.py:173-178 for this implementation:
         config.json / generation_config.json / model.safetensors.index.json + shards of the checkpoint directory.
@@ -188,7 +189,9 @@ class CogReasoner:
         ships with on GPUs; "eager" = the reference's CPU semantics (global attention + same-frame bias,
         modeling_videollama3_encoder.py:257-266), for parity runs; "sdpa" is broken in the reference (:348) and
         refused here. The model is built straight on `device` (default cuda:<current>): the later .to(local_rank)
-        of the reference driver (:183) is then a no-op."""
+        of the reference driver (:183) is then a no-op.
+        decode_weights="fp8": the Qwen2 linears are quantised to e4m3 on the device as they arrive (W8A16 decode,
+        Qwen2Engine); adapters loaded later follow."""
         from . import checkpoint as ck
         from .vision import BLOCK_DIAG, REF_EAGER_GLOBAL
         modes = {"flash_attention_2": BLOCK_DIAG, "eager": REF_EAGER_GLOBAL}
@@ -211,7 +214,7 @@ class CogReasoner:
         proj = Projector(proj_v, dtype=torch_dtype, device=dev)
         # load_llm=False: an encoder-only helper rank of a frame-sharded run (enable_sharded_encoder): the 15 GB of
         # Qwen2 weights are neither read nor held; everything else of the checkpoint must still be consumed
-        eng = Qwen2Engine(llm_v, cfgs["llm"], dtype=torch_dtype, device=dev) if load_llm else None
+        eng = Qwen2Engine(llm_v, cfgs["llm"], dtype=torch_dtype, device=dev, decode_weights=decode_weights) if load_llm else None
         reader.check_consumed(extra_ok=() if load_llm else tuple(llm_v._full(k) for k in llm_v))
         reader.close()
         # HF: generation_config.json, when present, IS the generation config (nothing is merged in from elsewhere);
@@ -258,7 +261,9 @@ class CogReasoner:
         copied, where the adapter does not touch them); lora_state: peft adapter_model state dict"""
         from .weights import merge_lora
         ml, mp = merge_lora(llm_state, proj_state, lora_state, self.config, lora_alpha)
-        llm = Qwen2Engine(ml, self.config, dtype=self.dtype, device=self.device)
+        base = self._adapters["base"][0]          # the adapter follows the base model: merged first, quantised after
+        llm = Qwen2Engine(ml, self.config, dtype=self.dtype, device=self.device,
+                          decode_weights=getattr(base, "decode_weights", None))
         proj = Projector(mp, dtype=self.dtype, device=self.device) if mp is not None else None
         self.add_adapter(adapter_name, llm, proj)
 

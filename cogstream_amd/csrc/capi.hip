@@ -32,6 +32,9 @@ struct cogs_ctx {
     bool llm_ok = false;
     cogs_llm_weights llm{};
     std::vector<cogs_llm_layer> llm_layers;
+    bool fp8_ok = false;            // cogs_llm_attach_fp8: e4m3 codes + row scales of the packed matrices
+    cogs_llm_fp8_weights fp8{};
+    std::vector<cogs_llm_fp8_layer> fp8_layers;
     float* llm_inv_freq = nullptr;  // device [head_dim/2]
     int llm_nfreq = 0; float llm_theta = 0.f;
     // pinned host staging for small host->device tables (segment boundaries): a ring of slots, each guarded by an
@@ -153,8 +156,9 @@ const char* cogs_status_string(cogs_status s) {
     }
 }
 
-// 0.2: cogs_gemm_desc.hm_rows / hm_cols, cogs_attn_desc.head_stride; 0.3: cogs_lm_score, cogs_row_lse
-const char* cogs_version(void) { return "cogstream_amd 0.3 (gfx950)"; }
+// 0.2: cogs_gemm_desc.hm_rows / hm_cols, cogs_attn_desc.head_stride; 0.3: cogs_lm_score, cogs_row_lse;
+// 0.4: cogs_gemv_fp8, cogs_quantize_fp8_rows, cogs_llm_attach_fp8
+const char* cogs_version(void) { return "cogstream_amd 0.4 (gfx950)"; }
 
 // ---------------------------------------------------------------- diagnostics (csrc/debug.h)
 // accepted range of a switch: on / off unless listed here
@@ -162,10 +166,11 @@ static bool cogs_debug_value_ok(const char* name, int64_t v) {
     struct Range { const char* name; int64_t lo, hi; };
     static const Range ranges[] = {
         {"gemm_wgs", 0, 256}, {"gemm_pad_pct", 100, 400}, {"gemm_group_m", 0, 64}, {"gemm_co_streams", 0, 8},
-        {"gemm_ring_cost_permille", 1, 4000}, {"gemv_small_n", 0, 1 << 30}, {"attn_vit", 0, 2}, {"attn_uniform_hint", 0, 1 << 20}, {"attn_prio", 0, 2},
+        {"gemm_ring_cost_permille", 1, 4000}, {"gemv_small_n", 0, 1 << 30}, {"gemv_fp8_load", 8, 16}, {"attn_vit", 0, 2}, {"attn_uniform_hint", 0, 1 << 20}, {"attn_prio", 0, 2},
         {"attn_nq", 0, 2}, {"vit_split_max", 0, INT64_MAX}, {"llm_split_keys", 0, 1 << 24}, {"km_row_groups", 0, 1 << 16},
         {"lm_score_rows", 1, 1 << 16}, {"lm_score_cols", 0, 1 << 24}, {"lm_score_split", 0, 4096},
     };
+    if (strcmp(name, "gemv_fp8_load") == 0 && v != 8 && v != 16) return false;
     for (const Range& r : ranges)
         if (strcmp(name, r.name) == 0) return v >= r.lo && v <= r.hi;
     return v == 0 || v == 1;
@@ -195,6 +200,7 @@ cogs_status cogs_debug_get(const char* name, int64_t* value) {
     if (strcmp(name, "lm_score_last_chunk") == 0) { *value = g_cogs_debug.lm_score_last_chunk; return COGS_OK; }
     if (strcmp(name, "lm_score_last_rows") == 0) { *value = g_cogs_debug.lm_score_last_rows; return COGS_OK; }
     if (strcmp(name, "lm_score_last_cols") == 0) { *value = g_cogs_debug.lm_score_last_cols; return COGS_OK; }
+    if (strcmp(name, "llm_last_decode_fp8") == 0) { *value = g_cogs_debug.llm_last_decode_fp8; return COGS_OK; }
     return COGS_E_INVALID;
 }
 
@@ -211,7 +217,8 @@ const char* cogs_debug_list(void) {
         "32-key blocks of the last tile (41 .. 72: compile-time shape), 0 the run-time form\n"
         "lm_score_last_split / lm_score_last_chunk / lm_score_last_rows / lm_score_last_cols (read only): the last cogs_lm_score / "
         "cogs_row_lse -- workgroups per row of a full panel in the fold kernel (1: no column split), columns per workgroup, rows and "
-        "columns of a panel\n";
+        "columns of a panel\n"
+        "llm_last_decode_fp8 (read only): 1 the last cogs_llm_forward / cogs_llm_forward_segments took the e4m3 GEMVs, 0 the weights' own type\n";
 }
 
 cogs_status cogs_create(int device, cogs_handle* out) {
@@ -268,6 +275,25 @@ cogs_status cogs_gemm(cogs_stream stream, const cogs_gemm_desc* d) {
     if (!d || !d->A || !d->W || !d->C) return COGS_E_INVALID;
     if (d->ln_ab && d->bias) return COGS_E_INVALID;     // col_c already contains the bias
     return cogs_k_gemm((hipStream_t)stream, to_gemm(d));
+}
+
+cogs_status cogs_gemv_fp8(cogs_stream stream, const cogs_gemv_fp8_desc* d) {
+    if (!d || !d->x || !d->W || !d->scale || !d->C) return COGS_E_INVALID;
+    CogsGemm g;
+    g.dtype = d->dtype;
+    g.A = d->x; g.lda = d->K; g.W = d->W; g.ldw = d->ldw; g.C = d->C; g.ldc = d->N;
+    g.bias = d->bias; g.residual = d->residual; g.ldr = d->N;
+    g.M = 1; g.N = d->N; g.K = d->K; g.act = d->act; g.out_f32 = d->out_f32;
+    g.rope_cos = d->rope_cos; g.rope_sin = d->rope_sin; g.rope_cols = d->rope_cols; g.head_dim = d->head_dim;
+    if (d->q_scale != 0.f) { g.q_scale = d->q_scale; g.q_cols = d->q_cols; }
+    g.rms_gamma = d->rms_gamma; g.rms_eps = d->rms_eps;
+    g.kv_k = d->kv_k; g.kv_v = d->kv_v; g.kv_col0 = d->kv_col0; g.kv_dim = d->kv_dim;
+    return cogs_k_gemv_fp8((hipStream_t)stream, g, d->scale);
+}
+
+cogs_status cogs_quantize_fp8_rows(cogs_stream stream, int dtype, const void* w, int64_t ldw, int N, int K, uint8_t* codes,
+                                   int64_t ldq, float* scale, void* dequant, int64_t ldd) {
+    return cogs_k_quantize_fp8_rows((hipStream_t)stream, dtype, w, ldw, N, K, codes, ldq, scale, dequant, ldd);
 }
 
 cogs_status cogs_ln_finalize(cogs_stream stream, const float* row_stats, int rows, int H, float eps, float* ln_ab) {
@@ -956,6 +982,7 @@ cogs_status cogs_llm_load(cogs_handle h, const cogs_llm_weights* w) {
     const int slab = w->dtype == COGS_DT_BF16 ? 64 : 32;
     if (w->hidden % slab || w->inter % slab || (w->heads * w->head_dim) % slab) return COGS_E_INVALID;
     h->llm = *w;
+    h->fp8_ok = false;      // the codes of cogs_llm_attach_fp8 belong to the weight set they were made from
     h->llm_layers.assign(w->layer, w->layer + w->layers);
     h->llm.layer = h->llm_layers.data();
     // Qwen2RotaryEmbedding: inv_freq = 1 / theta^(arange(0, hd, 2)/hd)
@@ -971,6 +998,23 @@ cogs_status cogs_llm_load(cogs_handle h, const cogs_llm_weights* w) {
         h->llm_nfreq = nf; h->llm_theta = w->rope_theta;
     }
     h->llm_ok = true;
+    return COGS_OK;
+}
+
+cogs_status cogs_llm_attach_fp8(cogs_handle h, const cogs_llm_fp8_weights* w) {
+    if (!h) return COGS_E_INVALID;
+    if (!w) { h->fp8_ok = false; return COGS_OK; }
+    if (!h->llm_ok || !w->layer || w->layers != h->llm.layers || !w->lm_head_q || !w->lm_head_s) return COGS_E_INVALID;
+    const cogs_llm_weights& m = h->llm;
+    if (m.hidden % 16 || m.inter % 16 || (m.heads * m.head_dim) % 16) return COGS_E_INVALID;
+    for (int l = 0; l < w->layers; ++l) {
+        const cogs_llm_fp8_layer& L = w->layer[l];
+        if (!L.qkv_q || !L.o_q || !L.gu_q || !L.down_q || !L.qkv_s || !L.o_s || !L.gu_s || !L.down_s) return COGS_E_INVALID;
+    }
+    h->fp8 = *w;
+    h->fp8_layers.assign(w->layer, w->layer + w->layers);
+    h->fp8.layer = h->fp8_layers.data();
+    h->fp8_ok = true;
     return COGS_OK;
 }
 
@@ -1063,8 +1107,18 @@ static cogs_status llm_forward_impl(cogs_handle h, cogs_stream stream, const voi
     { PROF(COGS_PROF_OTHER); COGS_TRY(cogs_k_llm_rope_table(st, rc, rs, nseg > 0 ? pos_d : nullptr, pos0, S, h->llm_inv_freq, hd / 2)); }
     const float scale = 1.0f / sqrtf((float)hd);
     const bool prescale_q = dt == COGS_DT_BF16 && hd == 128;   // see cogs_vit_encode
+    // single-token steps read the attached e4m3 codes (cogs_llm_attach_fp8); every other row count, and the lm_head GEMV
+    // behind a prompt, reads the (dequantised) matrices of cogs_llm_weights: prefill results do not depend on the mode
+    const bool fp8 = S == 1 && h->fp8_ok && g_cogs_debug.llm_decode_fp8 != 0;
+    g_cogs_debug.llm_last_decode_fp8 = fp8 ? 1 : 0;
+    auto linear = [&](CogsGemm& g, const uint8_t* codes, const float* scales) -> int {
+        if (!fp8) return cogs_k_gemm(st, g);
+        g.W = codes; g.ldw = g.K;
+        return cogs_k_gemv_fp8(st, g, scales);
+    };
     for (int l = 0; l < w.layers; ++l) {
         const cogs_llm_layer& L = h->llm_layers[l];
+        const cogs_llm_fp8_layer F = fp8 ? h->fp8_layers[l] : cogs_llm_fp8_layer{};
         const bool fuse_norm = (S == 1);   // single-token decode: RMSNorm runs inside the GEMV prologue
         const void* xin = (embeds_in_place && l == 0) ? embeds : (const void*)x;    // the residual stream entering this layer
         if (!fuse_norm) { PROF(COGS_PROF_NORM); COGS_TRY(cogs_k_rmsnorm(st, dt, x, ln, L.in_ln, S, H, w.rms_eps)); }
@@ -1080,7 +1134,7 @@ static cogs_status llm_forward_impl(cogs_handle h, cogs_stream stream, const voi
                 g.kv_v = (char*)kv->v + (((size_t)l * kv->max_len) + pos0) * kvd * es;
                 g.kv_col0 = qd_q; g.kv_dim = kvd;
             }
-            { PROF(COGS_PROF_GEMM); COGS_TRY(cogs_k_gemm(st, g)); }
+            { PROF(COGS_PROF_GEMM); COGS_TRY(linear(g, F.qkv_q, F.qkv_s)); }
         }
         const char* kp = (const char*)qkv + (size_t)qd_q * es;
         const char* vp = kp + (size_t)kvd * es;
@@ -1111,7 +1165,7 @@ static cogs_status llm_forward_impl(cogs_handle h, cogs_stream stream, const voi
             CogsGemm g; g.dtype = dt;
             g.A = att; g.lda = qd_q; g.W = L.o_w; g.ldw = qd_q; g.C = x; g.ldc = H;
             g.residual = xin; g.ldr = H; g.M = S; g.N = H; g.K = qd_q;
-            { PROF(COGS_PROF_GEMM); COGS_TRY(cogs_k_gemm(st, g)); }
+            { PROF(COGS_PROF_GEMM); COGS_TRY(linear(g, F.o_q, F.o_s)); }
         }
         if (!fuse_norm) { PROF(COGS_PROF_NORM); COGS_TRY(cogs_k_rmsnorm(st, dt, x, ln, L.post_ln, S, H, w.rms_eps)); }
         {
@@ -1119,13 +1173,13 @@ static cogs_status llm_forward_impl(cogs_handle h, cogs_stream stream, const voi
             g.A = fuse_norm ? x : ln; g.lda = H; g.W = L.gu_w; g.ldw = H; g.C = act; g.ldc = w.inter;
             g.M = S; g.N = 2 * w.inter; g.K = H; g.act = COGS_ACT_SWIGLU;
             if (fuse_norm) { g.rms_gamma = L.post_ln; g.rms_eps = w.rms_eps; }
-            { PROF(COGS_PROF_GEMM); COGS_TRY(cogs_k_gemm(st, g)); }
+            { PROF(COGS_PROF_GEMM); COGS_TRY(linear(g, F.gu_q, F.gu_s)); }
         }
         {
             CogsGemm g; g.dtype = dt;
             g.A = act; g.lda = w.inter; g.W = L.down_w; g.ldw = w.inter; g.C = x; g.ldc = H;
             g.residual = x; g.ldr = H; g.M = S; g.N = H; g.K = w.inter;
-            { PROF(COGS_PROF_GEMM); COGS_TRY(cogs_k_gemm(st, g)); }
+            { PROF(COGS_PROF_GEMM); COGS_TRY(linear(g, F.down_q, F.down_s)); }
         }
     }
     if (kv) kv->len = ctx;
@@ -1148,14 +1202,14 @@ static cogs_status llm_forward_impl(cogs_handle h, cogs_stream stream, const voi
             CogsGemm g; g.dtype = dt;
             g.A = (char*)hn + (size_t)(S - 1) * H * es; g.lda = H; g.W = w.lm_head; g.ldw = H; g.C = last_logits;
             g.ldc = w.vocab; g.M = 1; g.N = w.vocab; g.K = H; g.out_f32 = 1;
-            { PROF(COGS_PROF_GEMM); COGS_TRY(cogs_k_gemm(st, g)); }
+            { PROF(COGS_PROF_GEMM); COGS_TRY(linear(g, h->fp8.lm_head_q, h->fp8.lm_head_s)); }
         }
     } else if (last_logits) {
         CogsGemm g; g.dtype = dt;
         g.rms_gamma = w.final_norm; g.rms_eps = w.rms_eps;   // final RMSNorm fused into the lm_head GEMV
         g.A = (char*)x + (size_t)(S - 1) * H * es; g.lda = H; g.W = w.lm_head; g.ldw = H; g.C = last_logits; g.ldc = w.vocab;
         g.M = 1; g.N = w.vocab; g.K = H; g.out_f32 = 1;
-        { PROF(COGS_PROF_GEMM); COGS_TRY(cogs_k_gemm(st, g)); }
+        { PROF(COGS_PROF_GEMM); COGS_TRY(linear(g, h->fp8.lm_head_q, h->fp8.lm_head_s)); }
     }
     return COGS_OK;
 }

@@ -33,6 +33,8 @@
     X(gemm_headmajor, 1, "ViT encode: QKV GEMM writes q/k/v head-major [which][head][row][hd] for the attention kernel")    \
     X(gemv_small_n, 1024, "GEMV: 2 output rows per wave while N / 16 is below this (else 4)") \
     X(gemv_dot2, 1, "bf16 GEMV (decode): 1 products on v_dot2c_f32_bf16 from the packed registers (round 5), 0 unpack + fp32 fma per element") \
+    X(gemv_fp8_load, 8, "e4m3 GEMV (csrc/gemv_fp8.hip): bytes per weight load, 8 (K = 3584 is 7 x 64 chunks: register-resident fused RMSNorm) or 16") \
+    X(gemv_fp8_deep, 0, "e4m3 GEMV: 1 as many weight bytes in flight per lane as the bf16 GEMV (twice the loads), 0 as many loads (half the bytes; measured faster)") \
     /* ---- attention (csrc/attn.hip, attn_vit.hip, attn_decode.hip) ---- */                                                \
     X(attn_vit, 2, "ViT block-diagonal attention: 2 pipelined LDS-DMA kernel, 1 unpipelined, 0 general kernel")            \
     X(attn_vit_early, 0, "1: pipelined ViT kernel issues tiles 1-2 before its first wait (the order before round 4)")       \
@@ -48,6 +50,7 @@
     /* ---- encoder / LLM drivers (csrc/capi.hip), k-means ---- */                                                          \
     X(vit_split_max, 1099511627776LL, "clips above this many patches are encoded on one stream")                           \
     X(llm_split_keys, 0, "> 0: keys per split of the decode attention (0: chosen from the context)")                        \
+    X(llm_decode_fp8, 1, "cogs_llm_forward with e4m3 weights attached (cogs_llm_attach_fp8): 1 single-token steps read them, 0 the dequantised bf16 / fp32 copy (the in-process A/B)") \
     X(km_row_groups, 0, "> 0: row groups of the k-means distance pass (0: sized to fill the chip)")                       \
     /* ---- teacher-forced scoring (csrc/lm_score.hip) ---- */                                                              \
     X(lm_score_rows, 2048, "cogs_lm_score / cogs_row_lse: rows of a logits panel")                                          \
@@ -73,5 +76,7 @@ struct CogsDebug {
     std::atomic<long long> lm_score_last_chunk{0};
     std::atomic<long long> lm_score_last_rows{0};
     std::atomic<long long> lm_score_last_cols{0};
+    // ... and whether the last cogs_llm_forward / _segments took the e4m3 GEMVs (1) or the weights' own dtype (0)
+    std::atomic<long long> llm_last_decode_fp8{0};
 };
 extern CogsDebug g_cogs_debug;     // capi.hip

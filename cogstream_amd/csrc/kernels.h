@@ -49,6 +49,13 @@ struct CogsGemm {
                                              //   (include/cogs.h, cogs_gemm_desc.ln_ab, has the contract)
 };
 int cogs_k_gemm(hipStream_t st, const CogsGemm& g);
+// gemv_fp8.hip: M = 1 with W = OCP e4m3fn codes [N][ldw bytes] and one power-of-two fp32 scale per row; every other field as
+// for the GEMV behind cogs_k_gemm (rms_gamma, kv_k / kv_v, q_scale included); g.dtype = the activations' type
+int cogs_k_gemv_fp8(hipStream_t st, const CogsGemm& g, const float* scale);
+// rows of w [N][ldw] (bf16 / fp32) -> codes [N][ldq bytes], scale [N] = 2^ceil(log2(absmax / 448)) (1 for a zero row);
+// deq != null: also the dequantised rows in w's type (deq may be w)
+int cogs_k_quantize_fp8_rows(hipStream_t st, int dtype, const void* w, long ldw, int N, int K, uint8_t* codes, long ldq,
+                             float* scale, void* deq, long ldd);
 // (a, b) = (rstd, -rstd * mean) per row from the EPI_ROWSTAT partials [rows][tiles][2]: ab [rows][2]
 int cogs_k_ln_finalize(hipStream_t st, const float* stat_part, int rows, int tiles, int H, float eps, float* ab);
 

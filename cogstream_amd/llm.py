@@ -73,15 +73,23 @@ class PrefixKV:
 
 
 class Qwen2Engine:
-    def __init__(self, state: Dict[str, torch.Tensor], cfg: LlmConfig, dtype=torch.bfloat16, device="cuda"):
+    def __init__(self, state: Dict[str, torch.Tensor], cfg: LlmConfig, dtype=torch.bfloat16, device="cuda",
+                 decode_weights: Optional[str] = None):
+        """decode_weights="fp8": W8A16 decode -- single-token steps stream e4m3 codes of the linears (half the bytes), every
+        other pass reads the dequantised weights through the usual kernels (weights.PackedLlm / fp8_model_state)"""
         self.cfg, self.dtype, self.device = cfg, dtype, torch.device(device)
         self.handle = get_handle(self.device)
-        self.packed = PackedLlm(state, cfg, dtype, self.device)
+        self.packed = PackedLlm(state, cfg, dtype, self.device, decode_weights=decode_weights)
+        self.decode_weights = self.packed.decode_weights
         self._activate()
 
+    def _load(self):
+        L.check(L.lib.cogs_llm_load(self.handle.h, C.byref(self.packed.struct)), "cogs_llm_load")
+        if self.packed.fp8_struct is not None:
+            L.check(L.lib.cogs_llm_attach_fp8(self.handle.h, C.byref(self.packed.fp8_struct)), "cogs_llm_attach_fp8")
+
     def _activate(self):
-        self.handle.activate("llm", self, lambda: L.check(
-            L.lib.cogs_llm_load(self.handle.h, C.byref(self.packed.struct)), "cogs_llm_load"))
+        self.handle.activate("llm", self, self._load)
 
     def new_cache(self, max_len: int) -> KVCache:
         return KVCache(self.cfg, max_len, self.dtype, self.device)

@@ -75,6 +75,49 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, 
     return out
 
 
+def gemv_fp8(x: torch.Tensor, codes: torch.Tensor, scale: torch.Tensor, bias: Optional[torch.Tensor] = None, *,
+             act: int = L.ACT_NONE, residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+             out_f32: bool = False, rope_cos: Optional[torch.Tensor] = None, rope_sin: Optional[torch.Tensor] = None,
+             rope_cols: int = 0, head_dim: int = 0, q_scale: float = 0.0, q_cols: int = 0,
+             rms_gamma: Optional[torch.Tensor] = None, rms_eps: float = 0.0, kv_k: Optional[torch.Tensor] = None,
+             kv_v: Optional[torch.Tensor] = None, kv_col0: int = 0) -> torch.Tensor:
+    """out[N] = epilogue(scale[n] * (x[K] . e4m3(codes[N,K])))  (cogs_gemv_fp8 in include/cogs.h): the W8A16 decode GEMV.
+    x bf16 / fp32 [K] or [1, K]; codes uint8 [N, K] and scale fp32 [N] as quantize_fp8_rows makes them. kv_k / kv_v [kv_dim]:
+    the columns from kv_col0 on go there instead of `out`."""
+    _need_cuda(x, codes, scale, bias, residual, out, rope_cos, rope_sin, rms_gamma, kv_k, kv_v)
+    N, K = codes.shape
+    assert codes.dtype == torch.uint8 and codes.stride(1) == 1 and scale.dtype == torch.float32 and scale.is_contiguous()
+    assert x.numel() == K and x.is_contiguous() and scale.numel() == N
+    ncols = N // 2 if act == L.ACT_SWIGLU else N
+    if out is None:
+        out = torch.empty(ncols, device=x.device, dtype=torch.float32 if out_f32 else x.dtype)
+    d = L.GemvFp8Desc()
+    d.dtype = dtype_code(x.dtype)
+    d.x, d.W, d.ldw, d.scale, d.C = ptr(x), ptr(codes), codes.stride(0), ptr(scale), ptr(out)
+    d.bias, d.residual = ptr(bias), ptr(residual)
+    d.N, d.K, d.act, d.out_f32 = N, K, act, int(out_f32)
+    d.rope_cos, d.rope_sin, d.rope_cols, d.head_dim = ptr(rope_cos), ptr(rope_sin), rope_cols, head_dim
+    d.q_scale, d.q_cols = q_scale, q_cols
+    d.rms_gamma, d.rms_eps = ptr(rms_gamma), rms_eps
+    d.kv_k, d.kv_v, d.kv_col0 = ptr(kv_k), ptr(kv_v), kv_col0
+    d.kv_dim = kv_k.numel() if kv_k is not None else 0
+    check(L.lib.cogs_gemv_fp8(current_stream(), C.byref(d)), "cogs_gemv_fp8")
+    return out
+
+
+def quantize_fp8_rows(w: torch.Tensor, dequant: Optional[torch.Tensor] = None):
+    """device form of weights.quantize_fp8_rows (cogs_quantize_fp8_rows): w bf16 / fp32 [N, K] -> (codes uint8 [N, K], scale
+    fp32 [N]); dequant (may be w itself): the dequantised values are written there, in w's dtype"""
+    _need_cuda(w, dequant)
+    N, K = w.shape
+    assert w.stride(1) == 1 and (dequant is None or (dequant.shape == w.shape and dequant.dtype == w.dtype and dequant.stride(1) == 1))
+    codes = torch.empty(N, K, dtype=torch.uint8, device=w.device)
+    scale = torch.empty(N, dtype=torch.float32, device=w.device)
+    check(L.lib.cogs_quantize_fp8_rows(current_stream(), dtype_code(w.dtype), ptr(w), w.stride(0), N, K, ptr(codes), K, ptr(scale),
+                                       ptr(dequant), dequant.stride(0) if dequant is not None else 0), "cogs_quantize_fp8_rows")
+    return codes, scale
+
+
 def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, hq: int, hkv: int, head_dim: int,
               scale: Optional[float] = None, cu_seqlens: Optional[torch.Tensor] = None, max_seqlen: int = 0,
               row_lo: Optional[torch.Tensor] = None, row_hi: Optional[torch.Tensor] = None, bias: float = 0.0,

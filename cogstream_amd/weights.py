@@ -212,9 +212,80 @@ class PackedProjector:
         self.in_dim, self.out_dim = w.in_dim, w.out_dim
 
 
+# ---------------------------------------------------------------------------------------------------------
+# W8A16 decode weights: OCP e4m3fn codes with ONE power-of-two scale per output row. The host functions here are the
+# specification (and the oracle's model); the load path runs the same arithmetic in HIP (csrc/gemv_fp8.hip,
+# cogs_quantize_fp8_rows), bit for bit.
+
+FP8_MAX = 448.0          # largest e4m3fn magnitude (0x7E); 0x7F / 0xFF are NaN and never written
+FP8_LINEARS = ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.o_proj",
+               "mlp.gate_proj", "mlp.up_proj", "mlp.down_proj")
+
+
+def fp8_decode_table() -> torch.Tensor:
+    """fp32 [256]: the value of every e4m3fn code (torch's own cast: exact, every e4m3 value is an fp32 value)"""
+    return torch.arange(256, dtype=torch.int16).to(torch.uint8).view(torch.float8_e4m3fn).float()
+
+
+def fp8_row_scales(w: torch.Tensor) -> torch.Tensor:
+    """scale[n] = 2^ceil(log2(absmax_n / 448)), fp32 [N]; 1 for a zero row, never below 2^-126. Computed on the exponent
+    (absmax = m * 2^x with m in [0.5, 1), 448 = 0.875 * 2^9), not through log2: exact at the powers of two"""
+    absmax = w.detach().float().abs().amax(dim=1)
+    m, x = torch.frexp(absmax)
+    e = torch.where(m <= 0.875, x - 9, x - 8).clamp_min(-126)
+    e = torch.where(absmax > 0, e, torch.zeros_like(e))
+    return torch.ldexp(torch.ones_like(absmax), e)
+
+
+def quantize_fp8_rows(w: torch.Tensor):
+    """w [N, K] (any float dtype) -> (codes uint8 [N, K], scale fp32 [N]): codes = w / scale rounded to the nearest e4m3fn
+    value, ties to even (|w / scale| <= 448 by construction, so neither saturation nor a NaN code occurs)"""
+    if w.dim() != 2:
+        raise ValueError("quantize_fp8_rows takes a [N, K] matrix")
+    scale = fp8_row_scales(w)
+    codes = (w.detach().float() / scale[:, None]).to(torch.float8_e4m3fn).view(torch.uint8)
+    return codes.contiguous(), scale.contiguous()
+
+
+def dequantize_fp8_rows(codes: torch.Tensor, scale: torch.Tensor, dtype=torch.float32) -> torch.Tensor:
+    """code * scale: at most 4 significant bits, so exact in fp32 and in bf16"""
+    v = codes.contiguous().view(torch.float8_e4m3fn).float() * scale.float()[:, None]
+    return v.to(dtype)
+
+
+def fp8_model_state(llm_state: Dict[str, torch.Tensor], dtype=None) -> Dict[str, torch.Tensor]:
+    """the HF-named state dict of the model decode_weights="fp8" evaluates: q/k/v/o/gate/up/down_proj.weight of every layer
+    and lm_head.weight replaced by their dequantised values, embeddings / norms / biases shared. `dtype`: the engine's
+    dtype when it differs from the tensors' -- PackedLlm rounds a weight to its dtype BEFORE quantising, so does this
+    (rounding an fp32 weight to bf16 first can move its e4m3 code); the returned tensors keep their own dtype, which holds
+    the dequantised values exactly. Per-row quantisation commutes with the packing (row interleaves and stacking), so
+    this is what PackedLlm holds."""
+    out = dict(llm_state)
+    for k, w in llm_state.items():
+        if k == "lm_head.weight" or (k.startswith("layers.") and any(k.endswith(t + ".weight") for t in FP8_LINEARS)):
+            src = w if dtype is None else w.to(dtype)
+            out[k] = dequantize_fp8_rows(*quantize_fp8_rows(src), dtype=w.dtype)
+    return out
+
+
 class PackedLlm:
-    def __init__(self, state: Dict[str, torch.Tensor], cfg: LlmConfig, dtype=torch.bfloat16, device="cuda"):
+    def __init__(self, state: Dict[str, torch.Tensor], cfg: LlmConfig, dtype=torch.bfloat16, device="cuda",
+                 decode_weights: Optional[str] = None):
+        """decode_weights="fp8": every packed linear (qkv, o, gate/up, down, lm_head) is quantised row by row to e4m3 codes +
+        power-of-two scales for the single-token GEMVs, and the matrix the M > 1 kernels read is REPLACED by the dequantised
+        values, so prefill and decode evaluate one model (fp8_model_state); both copies stay in HBM. None / "bf16": off."""
         self.cfg, self.dtype, self.device = cfg, dtype, torch.device(device)
+        if decode_weights in (None, "bf16", "none"):
+            decode_weights = None
+        elif decode_weights != "fp8":
+            raise ValueError(f"decode_weights={decode_weights!r}: use None or 'fp8'")
+        self.decode_weights = decode_weights
+        if decode_weights:
+            qd_q = cfg.num_attention_heads * cfg.head_dim
+            bad = {n: v for n, v in (("hidden_size", cfg.hidden_size), ("intermediate_size", cfg.intermediate_size),
+                                     ("heads * head_dim", qd_q)) if v % 16}
+            if bad:
+                raise ValueError(f"decode_weights='fp8' needs K % 16 == 0 (16-byte rows of codes) for every linear: {bad}")
         hd, hq, hkv = cfg.head_dim, cfg.num_attention_heads, cfg.num_key_value_heads
         cv = lambda t: t.to(device=self.device, dtype=dtype)
         self.keep: List[torch.Tensor] = []
@@ -224,10 +295,37 @@ class PackedLlm:
             self.keep.append(t)
             return t
 
+        self.fp8_layers = (L.LlmFp8Layer * cfg.num_hidden_layers)() if decode_weights else None
+        self.fp8_codes: Dict[str, torch.Tensor] = {}     # packed name ("lm_head", "layers.3.qkv", ...) -> uint8 [N, K]
+        self.fp8_scales: Dict[str, torch.Tensor] = {}
+
+        def lin(name, t):
+            """a packed linear: held as is, or -- fp8 mode -- quantised, held dequantised, codes and scales kept beside it"""
+            t = hold(t)
+            if not decode_weights:
+                return t, None, None
+            if t.is_cuda:
+                from .ops import quantize_fp8_rows as quant_dev
+                if t.data_ptr() % 16 or not t.is_contiguous():
+                    t = hold(t.clone(memory_format=torch.contiguous_format))
+                codes, scale = quant_dev(t, dequant=t)         # in place: t now holds code * scale
+            else:
+                codes, scale = quantize_fp8_rows(t)
+                t.copy_(dequantize_fp8_rows(codes, scale, dtype=t.dtype))
+            self.fp8_codes[name], self.fp8_scales[name] = hold(codes), hold(scale)
+            return t, codes, scale
+
         g = lambda k: cv(state[k])
+
+        def own(k):
+            """g(k) as a tensor this object may overwrite (fp8 mode dequantises in place): never the caller's own storage"""
+            src = state[k]
+            t = cv(src)
+            return t.clone() if decode_weights and t.data_ptr() == src.data_ptr() else t
+
         self.embed = hold(g("embed_tokens.weight"))
         self.final_norm = hold(g("norm.weight"))
-        self.lm_head = hold(g("lm_head.weight"))
+        self.lm_head, lm_q, lm_s = lin("lm_head", own("lm_head.weight"))
         self.layers = (L.LlmLayer * cfg.num_hidden_layers)()
         for i in range(cfg.num_hidden_layers):
             p = f"layers.{i}."
@@ -236,13 +334,20 @@ class PackedLlm:
             kw, kb = _perm_heads(g(a + "k_proj.weight"), hkv, hd), _perm_heads(g(a + "k_proj.bias"), hkv, hd)
             lay = self.layers[i]
             lay.in_ln = hold(g(p + "input_layernorm.weight")).data_ptr()
-            lay.qkv_w = hold(torch.cat([qw, kw, g(a + "v_proj.weight")], 0)).data_ptr()
+            mats = {}
+            mats["qkv"] = lin(p + "qkv", torch.cat([qw, kw, g(a + "v_proj.weight")], 0))
             lay.qkv_b = hold(torch.cat([qb, kb, g(a + "v_proj.bias")], 0)).data_ptr()
-            lay.o_w = hold(g(a + "o_proj.weight")).data_ptr()
+            mats["o"] = lin(p + "o", own(a + "o_proj.weight"))
             lay.post_ln = hold(g(p + "post_attention_layernorm.weight")).data_ptr()
             gu = torch.stack([g(p + "mlp.gate_proj.weight"), g(p + "mlp.up_proj.weight")], dim=1)
-            lay.gu_w = hold(gu.reshape(2 * cfg.intermediate_size, cfg.hidden_size)).data_ptr()
-            lay.down_w = hold(g(p + "mlp.down_proj.weight")).data_ptr()
+            mats["gu"] = lin(p + "gu", gu.reshape(2 * cfg.intermediate_size, cfg.hidden_size))
+            mats["down"] = lin(p + "down", own(p + "mlp.down_proj.weight"))
+            lay.qkv_w, lay.o_w, lay.gu_w, lay.down_w = (mats[n][0].data_ptr() for n in ("qkv", "o", "gu", "down"))
+            if decode_weights:
+                f = self.fp8_layers[i]
+                for n in ("qkv", "o", "gu", "down"):
+                    setattr(f, n + "_q", mats[n][1].data_ptr())
+                    setattr(f, n + "_s", mats[n][2].data_ptr())
         w = L.LlmWeights()
         w.dtype = L.dtype_code(dtype)
         w.hidden, w.inter, w.layers = cfg.hidden_size, cfg.intermediate_size, cfg.num_hidden_layers
@@ -251,6 +356,17 @@ class PackedLlm:
         w.final_norm, w.lm_head = self.final_norm.data_ptr(), self.lm_head.data_ptr()
         w.layer = C.cast(self.layers, C.POINTER(L.LlmLayer))
         self.struct = w
+        self.fp8_struct = None
+        if decode_weights:
+            f8 = L.LlmFp8Weights()
+            f8.layers, f8.lm_head_q, f8.lm_head_s = cfg.num_hidden_layers, lm_q.data_ptr(), lm_s.data_ptr()
+            f8.layer = C.cast(self.fp8_layers, C.POINTER(L.LlmFp8Layer))
+            self.fp8_struct = f8
+
+    @property
+    def fp8_bytes(self) -> int:
+        """bytes of e4m3 codes held for the decode GEMVs (one per weight of every quantised linear); 0 when the mode is off"""
+        return sum(t.numel() for t in self.fp8_codes.values())
 
 
 # ---- random initialisation at arbitrary dimensions (no checkpoints are reachable: README.md:56-58) ----

@@ -90,7 +90,8 @@ const char* cogs_debug_list(void);
  * (`cogs_gemm_desc d = {0};` / memset / ctypes' default constructor): they carry no size or version member, new optional
  * fields are appended at the end with 0 = "off" (round 5: cogs_gemm_desc.hm_rows / hm_cols, cogs_attn_desc.head_stride), and a
  * field left holding stack garbage switches a feature on. cogs_version() names the ABI revision: "0.2" added those three,
- * "0.3" cogs_lm_score / cogs_row_lse (new entry points only; every older signature is unchanged). */
+ * "0.3" cogs_lm_score / cogs_row_lse, "0.4" cogs_gemv_fp8 / cogs_quantize_fp8_rows / cogs_llm_attach_fp8 (new entry points
+ * only; every older signature and structure is unchanged). */
 
 /* C[M,N] = epilogue(A[M,K] . W[N,K]^T). nn.Linear / Conv2d(k=s=14) replacement
  * (model/modeling_videollama3_encoder.py:194-210,246-248,275,369-373; cogreasoner_chat.py:179-211).
@@ -162,6 +163,46 @@ typedef struct {
 cogs_status cogs_gemm(cogs_stream stream, const cogs_gemm_desc* d);
 /* (rstd, -rstd * mean) per row from the row_stats partials of a GEMM whose N is the LayerNorm width H */
 cogs_status cogs_ln_finalize(cogs_stream stream, const float* row_stats, int rows, int H, float eps, float* ln_ab);
+
+/* W8A16 GEMV (single-token decode): C[N] = epilogue(scale[n] * sum_k x[k] * e4m3(W[n][k])). W holds OCP e4m3fn codes (one
+ * byte per weight; 0x7F / 0xFF, the NaN codes, must not occur), scale one fp32 POWER OF TWO per output row -- what
+ * cogs_quantize_fp8_rows writes -- so that a dequantised weight code * scale is exactly a bf16 value and the GEMV computes
+ * what cogs_gemm computes on the dequantised matrix (other summation order). dtype (COGS_DT_*) is the type of x, bias,
+ * residual, rms_gamma, C and the K / V row; sums are fp32. Epilogue as cogs_gemm with M = 1: bias, rotary (row tables
+ * [head_dim/2], or one interleaved table when rope_sin == NULL) on columns < rope_cols, q_scale (0 or 1 = off) on columns <
+ * q_cols, act, residual (may alias C), out_f32. rms_gamma != NULL: x is replaced by Qwen2RMSNorm(x) = gamma * (x *
+ * rsqrt(mean(x^2) + rms_eps)) on the fly. kv_k != NULL: columns [kv_col0, kv_col0 + kv_dim) are written to kv_k[0..kv_dim)
+ * and the next kv_dim columns to kv_v instead of C (kv_col0 + 2 * kv_dim == N; not with out_f32 / SWIGLU).
+ * COGS_E_INVALID: a NULL x / W / scale / C, N % 4 != 0, K % 16 != 0, ldw % 16 != 0 or ldw < K, x / W / rms_gamma not 16-byte
+ * aligned, a kv_col0 / kv_dim that is not a multiple of 4, and what cogs_gemm rejects for the same epilogue. */
+typedef struct {
+    int dtype;
+    const void* x;                       /* [K] */
+    const uint8_t* W; int64_t ldw;       /* [N][ldw] bytes */
+    const float* scale;                  /* [N] */
+    void* C;                             /* [N] (SWIGLU: [N/2]) */
+    const void* bias;                    /* [N], nullable */
+    const void* residual;                /* [N], nullable */
+    int N, K;
+    int act;
+    int out_f32;
+    const float* rope_cos;
+    const float* rope_sin;
+    int rope_cols;
+    int head_dim;
+    float q_scale; int q_cols;
+    const void* rms_gamma; float rms_eps;
+    void* kv_k; void* kv_v; int kv_col0; int kv_dim;
+} cogs_gemv_fp8_desc;
+cogs_status cogs_gemv_fp8(cogs_stream stream, const cogs_gemv_fp8_desc* d);
+
+/* Row-wise e4m3 quantiser of the load path: w [N][ldw] (dtype bf16 / fp32, ldw in elements) -> codes [N][ldq] bytes and
+ * scale [N] fp32 with scale[n] = 2^ceil(log2(absmax_n / 448)) (1 for an all-zero row, never below 2^-126), codes = w / scale
+ * rounded to the nearest e4m3fn value, ties to even. dequant (nullable; may be w itself; ldd in elements): code * scale in
+ * `dtype`, exact. Bit-equal to cogstream_amd.weights.quantize_fp8_rows, which is its specification. K % 16 == 0, rows of w /
+ * dequant 16-byte aligned, ldq % 8 == 0, else COGS_E_INVALID. */
+cogs_status cogs_quantize_fp8_rows(cogs_stream stream, int dtype, const void* w, int64_t ldw, int N, int K, uint8_t* codes,
+                                   int64_t ldq, float* scale, void* dequant, int64_t ldd);
 
 /* Attention over token-major Q/K/V (row stride ld*, head h at column h*head_dim).
  * cu_seqlens (device int32 [nseg+1], nullable): block-diagonal segments as in
@@ -422,6 +463,24 @@ typedef struct {
     const cogs_llm_layer* layer; /* host array [layers] */
 } cogs_llm_weights;
 cogs_status cogs_llm_load(cogs_handle h, const cogs_llm_weights* w);
+
+/* e4m3 copies of the packed matrices of the loaded model (cogs_quantize_fp8_rows layout: codes [N][K] dense, scale [N]), in
+ * the packing of cogs_llm_layer. While attached, a cogs_llm_forward / _segments over ONE token reads them through
+ * cogs_gemv_fp8 instead of the matrices of cogs_llm_weights; every M > 1 GEMM and cogs_lm_score keep reading the latter,
+ * which the caller has replaced by the dequantised values so that both evaluate one model. NULL detaches; cogs_llm_load
+ * detaches too (the codes belong to one weight set). Needs hidden, inter and heads * head_dim to be multiples of 16.
+ * Debug switch llm_decode_fp8 = 0: single-token steps go through the dequantised matrices again (in-process A/B);
+ * cogs_debug_get("llm_last_decode_fp8") says what the last forward took. */
+typedef struct {
+    const uint8_t *qkv_q, *o_q, *gu_q, *down_q;
+    const float *qkv_s, *o_s, *gu_s, *down_s;
+} cogs_llm_fp8_layer;
+typedef struct {
+    int layers;
+    const uint8_t* lm_head_q; const float* lm_head_s;
+    const cogs_llm_fp8_layer* layer; /* host array [layers] */
+} cogs_llm_fp8_weights;
+cogs_status cogs_llm_attach_fp8(cogs_handle h, const cogs_llm_fp8_weights* w);
 
 /* KV cache, caller-owned: k and v are [layers][max_len][kv_heads*head_dim] in the weights' dtype */
 typedef struct {

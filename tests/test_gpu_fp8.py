@@ -1,0 +1,558 @@
+"""decode_weights="fp8" on the GPU: the e4m3 GEMV (csrc/gemv_fp8.hip) cell by cell against the fp64 reference of
+tests/gemm_reference.py computed from the DEQUANTISED weights, the device quantiser against the host one bit for bit, and
+the engines / the loaded product against the same code (or the CPU oracle) run on weights.fp8_model_state -- the one model
+both prefill and decode evaluate when the mode is on."""
+from __future__ import annotations
+
+import contextlib
+import ctypes as C
+import math
+
+import pytest
+import torch
+
+import gemm_reference as R
+from conftest import rel_err
+from test_fp8_host import _formula_table, _inputs
+
+pytestmark = pytest.mark.gpu
+
+BF16, F32 = torch.bfloat16, torch.float32
+TRACE16, TRACE32 = 0x7F7F, 0x7F7F7F7F        # finite tracer patterns, as in test_gpu_gemm_conformance.py
+HD = 128
+
+
+def _L():
+    from cogstream_amd import _lib
+    return _lib
+
+
+@contextlib.contextmanager
+def switches(**kw):
+    L = _L()
+    with contextlib.ExitStack() as st:
+        for k, v in kw.items():
+            st.enter_context(L.debug_switch(k, v))
+        yield
+
+
+def _filled(n, dtype, dev):
+    if dtype == F32:
+        return torch.full((n,), TRACE32, dtype=torch.int32, device=dev).view(F32)
+    return torch.full((n,), TRACE16, dtype=torch.int16, device=dev).view(dtype)
+
+
+def _bits(t):
+    return t.view(torch.int32) if t.element_size() == 4 else t.view(torch.int16)
+
+
+# every kernel instance: (bytes per load, depth) x rows per wave (gemv_small_n = 0 forces 4 rows per wave at any N); the first
+# entry is the shipped default
+VARIANTS = [dict(gemv_fp8_load=8, gemv_fp8_deep=0), dict(gemv_fp8_load=8, gemv_fp8_deep=1),
+            dict(gemv_fp8_load=16, gemv_fp8_deep=1), dict(gemv_fp8_load=16, gemv_fp8_deep=0)]
+
+
+# ----------------------------------------------------------------------------------------------------------- 1. decode table
+@pytest.mark.parametrize("dtype", [BF16, F32], ids=["bf16", "fp32"])
+def test_decode_table_through_the_kernel(dev, dtype):
+    """every finite e4m3fn code times 1.0, alone in its row, at four row scales: the output must be EXACTLY table * scale
+    (this is what decides that the hardware conversions read OCP e4m3fn and that the scale is applied exactly)"""
+    from cogstream_amd import ops
+    tab = _formula_table()
+    finite = (~torch.isnan(tab)).nonzero().view(-1)
+    assert finite.numel() == 254
+    for K in (16, 64):
+        codes = torch.zeros(256, K, dtype=torch.uint8)
+        codes[finite, (finite * 5) % K] = finite.to(torch.uint8)
+        codes = codes[finite].contiguous().to(dev)                        # N = 254 is not a multiple of 4 -> pad to 256 rows
+        codes = torch.cat([codes, codes[:2]], 0).contiguous()
+        want_unit = torch.cat([tab[finite], tab[finite][:2]])
+        x = torch.ones(K, dtype=dtype, device=dev)
+        for s in (2.0 ** -20, 2.0 ** -9, 1.0, 8.0):
+            scale = torch.full((256,), s, dtype=F32, device=dev)
+            for var in VARIANTS:
+                for small_n in (1024, 0):
+                    with switches(gemv_small_n=small_n, **var):
+                        out = ops.gemv_fp8(x, codes, scale)
+                        out32 = ops.gemv_fp8(x, codes, scale, out_f32=True)
+                    for o in (out, out32):
+                        got = o.double().cpu()
+                        assert torch.equal(got, want_unit * s), (K, s, var, small_n, (got != want_unit * s).nonzero().view(-1)[:8].tolist())
+
+
+# ----------------------------------------------------------------------------------------------------------- 2. conformance
+def _quantised(dev, N, K, dtype, seed):
+    """codes / scales of a random matrix with row magnitudes spread over 2^-3 .. 2^3 (so the scales differ), its dequantised
+    values in `dtype` (exact) -- from the FORMULA table, not from a cast -- and a generator"""
+    from cogstream_amd.weights import quantize_fp8_rows
+    g = torch.Generator(device=dev).manual_seed(seed)
+    w = torch.randn(N, K, generator=g, device=dev) / math.sqrt(K)
+    w = w * torch.exp2(torch.randint(-3, 4, (N, 1), generator=g, device=dev).float())
+    codes, scale = quantize_fp8_rows(w)
+    del w
+    tab = _formula_table().to(dev)
+    assert not bool(((codes & 0x7F) == 0x7F).any())
+    deq = torch.empty(N, K, dtype=dtype, device=dev)
+    for r0 in range(0, N, 16384):
+        v = tab[codes[r0:r0 + 16384].long()] * scale[r0:r0 + 16384].double()[:, None]
+        deq[r0:r0 + 16384] = v.to(dtype)
+        assert torch.equal(deq[r0:r0 + 16384].double(), v)                 # dequantised weights are exact in bf16 and fp32
+    return codes, scale, deq, g
+
+
+def _rmsnorm_rows(x, gamma, eps, rel):
+    """Qwen2RMSNorm of the single row x in the kernel's arithmetic (csrc/norm.hip): rstd in fp32 from the fp64 mean square,
+    times (1 + rel); bf16: weight * (x * rstd).to(bf16), rounded to bf16 again; fp32: weight * (x * rstd)"""
+    rstd = (1.0 / torch.sqrt(x.double().pow(2).mean() + eps) * (1.0 + rel)).float()
+    n = x.float() * rstd
+    if x.dtype == BF16:
+        n = n.to(BF16).float()
+    n = gamma.float() * n
+    return n.to(x.dtype)
+
+
+def run_cell(dev, N, K, *, dtype=BF16, bias=False, res=None, act=R.ACT_NONE, out_f32=False, rope=None, rope_cols=0,
+             q_cols=0, kv_dim=0, rms=False, seed=1, **sw):
+    """one cogs_gemv_fp8 through the C ABI; every output element against its own fp64 band, guards bit for bit.
+    res: None | "sep" | "inplace"; rope: None | "inter" | "sep"; q_cols > 0: q_scale = 2^-3 on the columns below it;
+    kv_dim > 0: the last 2 * kv_dim columns are the new K / V cache row"""
+    L = _L()
+    codes, scale, deq, g = _quantised(dev, N, K, dtype, seed)
+    x = (torch.randn(K, generator=g, device=dev) * 0.7 + 0.1).to(dtype)
+    swiglu = act == R.ACT_SWIGLU
+    ocols = N // 2 if swiglu else N
+    odt = F32 if (out_f32 or dtype == F32) else dtype
+    d = L.GemvFp8Desc()
+    d.dtype = L.dtype_code(dtype)
+    d.x, d.W, d.ldw, d.scale = x.data_ptr(), codes.data_ptr(), K, scale.data_ptr()
+    d.N, d.K, d.act, d.out_f32 = N, K, act, int(out_f32)
+    a = x.view(1, K)
+    extra = None
+    if rms:
+        eps = 1e-6
+        gamma = (1 + 0.1 * torch.randn(K, generator=g, device=dev)).to(dtype)
+        d.rms_gamma, d.rms_eps = gamma.data_ptr(), eps
+        a = _rmsnorm_rows(x, gamma, eps, 0.0).view(1, K)
+        # The device's rstd is an fp32 computation: every lane adds its K / 64 squares in sequence, six butterfly levels join
+        # the lanes, then a division, the eps addition and v_rsq_f32 (1 ulp). Worst case, relative to the exact rstd:
+        # half of (K / 64 + 9) roundings of 2^-24 on the sum, plus 2^-23 + 2^-24. That scales a (fp32), or moves an element by
+        # a bf16 step where x * rstd lies that close to a rounding boundary (bf16; the rounding is monotonic in rstd, so the
+        # two ends of the interval decide). What the ends change enters the tolerance through |W|: nothing when no element
+        # is near a boundary.
+        rel = 0.5 * (K / 64 + 9) * 2.0 ** -24 + 2.0 ** -23 + 2.0 ** -24
+        lo, hi = _rmsnorm_rows(x, gamma, eps, -rel), _rmsnorm_rows(x, gamma, eps, rel)
+        extra = ((hi.double() - lo.double()).abs().view(1, K) @ deq.double().abs().t())
+    acc, bound = R.product_and_bound(a, deq)
+    if extra is not None:
+        bound = bound + extra
+    bias_t = None
+    if bias:
+        bias_t = torch.randn(N, generator=g, device=dev).to(dtype)
+        d.bias = bias_t.data_ptr()
+    rope_r = None
+    keep = []
+    if rope:
+        ang = torch.rand(1, HD // 2, generator=g, device=dev) * 6.0
+        cos, sin = ang.cos(), ang.sin()
+        if rope == "sep":
+            tc, ts = cos.contiguous(), sin.contiguous()
+            d.rope_cos, d.rope_sin = tc.data_ptr(), ts.data_ptr()
+            keep += [tc, ts]
+        else:
+            tc = torch.stack([cos, sin], -1).contiguous()
+            d.rope_cos = tc.data_ptr()
+            keep.append(tc)
+        d.rope_cols, d.head_dim = rope_cols, HD
+        rope_r = R.Rope(cos.double(), sin.double(), rope_cols, HD)
+    bias_ref = bias_t
+    if q_cols:
+        # tests/gemm_reference.py has no q_scale step. With a power of two the step commutes exactly with every rounding
+        # around it, so the reference runs on pre-scaled columns: q * rope(acc + bias) = rope(q * acc + q * bias)
+        qs = 0.125
+        d.q_scale, d.q_cols = qs, q_cols
+        colscale = torch.where(torch.arange(N, device=dev) < q_cols, qs, 1.0).double()
+        acc, bound = acc * colscale[None, :], bound * colscale[None, :]
+        bias_ref = bias_t.double() * colscale if bias_t is not None else None
+    cbuf = _filled(64 + ocols + 64, odt, dev)
+    cview = cbuf[64:64 + ocols]
+    d.C = cview.data_ptr()
+    inside = torch.zeros(cbuf.numel(), dtype=torch.bool, device=dev)
+    inside[64:64 + ocols] = True
+    res_t = None
+    if res == "sep":
+        res_t = torch.randn(N, generator=g, device=dev).to(dtype)
+        d.residual = res_t.data_ptr()
+    elif res == "inplace":
+        res_t = torch.randn(N, generator=g, device=dev).to(dtype)
+        cview.copy_(res_t)
+        d.residual = cview.data_ptr()
+    kvbuf = None
+    if kv_dim:
+        kvbuf = _filled(2 * (32 + kv_dim + 32), dtype, dev)
+        kk, vv = kvbuf[32:32 + kv_dim], kvbuf[32 + kv_dim + 64:32 + kv_dim + 64 + kv_dim]
+        d.kv_k, d.kv_v, d.kv_col0, d.kv_dim = kk.data_ptr(), vv.data_ptr(), N - 2 * kv_dim, kv_dim
+        kv_inside = torch.zeros(kvbuf.numel(), dtype=torch.bool, device=dev)
+        kv_inside[32:32 + kv_dim] = True
+        kv_inside[32 + kv_dim + 64:32 + kv_dim + 64 + kv_dim] = True
+        kv_guard = _bits(kvbuf)[~kv_inside].clone()
+        inside[64 + N - 2 * kv_dim:64 + N] = False                          # those columns of C must stay untouched
+    guard = _bits(cbuf)[~inside].clone()
+    ref, tol = R.epilogue(acc, bound, bias=bias_ref, rope=rope_r, act=act,
+                          residual=res_t.view(1, -1) if res_t is not None else None, out_f32=out_f32, out_dtype=odt)
+    with switches(**sw):
+        rc = L.lib.cogs_gemv_fp8(L.current_stream(), C.byref(d))
+    assert rc == 0, (rc, N, K, sw)
+    torch.cuda.synchronize()
+    what = f"gemv_fp8 N={N} K={K} {dtype} bias={bias} res={res} act={act} f32={out_f32} rope={rope} q={q_cols} kv={kv_dim} rms={rms} {sw}"
+    assert torch.equal(_bits(cbuf)[~inside], guard), what + ": guard elements around C changed"
+    if kv_dim:
+        assert torch.equal(_bits(kvbuf)[~kv_inside], kv_guard), what + ": guard elements around the K / V row changed"
+        c0 = N - 2 * kv_dim
+        R.assert_within(cview[:c0].view(1, -1), ref[:, :c0], tol[:, :c0], what)
+        R.assert_within(kk.view(1, -1), ref[:, c0:c0 + kv_dim], tol[:, c0:c0 + kv_dim], what + " (K row)")
+        R.assert_within(vv.view(1, -1), ref[:, c0 + kv_dim:], tol[:, c0 + kv_dim:], what + " (V row)")
+    else:
+        R.assert_within(cview.view(1, -1), ref, tol, what)
+    del keep
+
+
+@pytest.mark.parametrize("N", [132, 16380, 16384, 16388])
+@pytest.mark.parametrize("dtype", [BF16, F32], ids=["bf16", "fp32"])
+def test_n_edges(dev, N, dtype):
+    """the cells of test_gemv_edges: whole and ragged last workgroups on both sides of the 2 / 4 rows-per-wave switch"""
+    for var in (VARIANTS[1], VARIANTS[3]):
+        run_cell(dev, N, 256, dtype=dtype, bias=True, res="sep", **var)
+        run_cell(dev, N, 256, dtype=dtype, bias=True, res="inplace", **var)
+        run_cell(dev, N, 256, dtype=dtype, act=R.ACT_SWIGLU, **var)
+
+
+@pytest.mark.parametrize("K", [16, 48, 1008, 1040, 3584, 18944])
+@pytest.mark.parametrize("dtype", [BF16, F32], ids=["bf16", "fp32"])
+def test_k_edges(dev, K, dtype):
+    """fewer chunks than lanes, ragged tails behind whole batches, the model's two K -- on every kernel instance"""
+    for var in VARIANTS:
+        for small_n in (1024, 0):
+            run_cell(dev, 264, K, dtype=dtype, bias=True, res="sep", seed=K, gemv_small_n=small_n, **var)
+
+
+@pytest.mark.parametrize("epi", ["qkv", "qkv sep", "res", "res in place", "swiglu", "f32out"])
+def test_decode_epilogues_at_the_lm_head_width(dev, epi):
+    """what llm_forward_impl asks of the GEMV, at N = 152 064: bias + rotary + q_scale + the K / V row written into the cache
+    (1100 + 2 x 44 heads of 128), the residual separate and in place, SwiGLU, fp32 logits"""
+    N = 152064
+    kvd = 44 * HD
+    kw = {"qkv": dict(bias=True, rope="inter", rope_cols=N - kvd, q_cols=N - 2 * kvd, kv_dim=kvd),
+          "qkv sep": dict(bias=True, rope="sep", rope_cols=N - kvd, q_cols=N - 2 * kvd, kv_dim=kvd),
+          "res": dict(res="sep"), "res in place": dict(res="inplace"), "swiglu": dict(act=R.ACT_SWIGLU),
+          "f32out": dict(out_f32=True)}[epi]
+    run_cell(dev, N, 512, **kw)
+
+
+@pytest.mark.parametrize("K", [3584, 1040])
+@pytest.mark.parametrize("dtype", [BF16, F32], ids=["bf16", "fp32"])
+def test_fused_rmsnorm(dev, K, dtype):
+    """the Qwen2RMSNorm prologue: register-resident at K = 3584 (bf16, 8-byte loads), the generic form everywhere else -- in
+    the three forms the model uses (qkv, gate / up, lm_head), 2 and 4 rows per wave"""
+    kvd = 2 * HD
+    N = 6 * HD + 2 * kvd
+    for var in (VARIANTS[1], VARIANTS[0], VARIANTS[2]):
+        for small_n in (1024, 0):
+            sw = dict(gemv_small_n=small_n, **var)
+            run_cell(dev, N, K, dtype=dtype, rms=True, bias=True, rope="inter", rope_cols=N - kvd, q_cols=N - 2 * kvd, kv_dim=kvd, seed=K + 1, **sw)
+            run_cell(dev, 1032, K, dtype=dtype, rms=True, act=R.ACT_SWIGLU, seed=K + 2, **sw)
+            run_cell(dev, 1028, K, dtype=dtype, rms=True, out_f32=True, seed=K + 3, **sw)
+
+
+def test_invalid_descriptors_return_their_status_before_any_launch(dev):
+    L = _L()
+    N, K = 64, 64
+    codes = torch.zeros(N + 1, K + 16, dtype=torch.uint8, device=dev)
+    scale = torch.ones(N, device=dev)
+    x = torch.ones(K + 16, dtype=BF16, device=dev)
+    out = _filled(N + 64, BF16, dev)
+    kv = _filled(64, BF16, dev)
+    before, kv_before = _bits(out).clone(), _bits(kv).clone()
+
+    def desc(**kw):
+        d = L.GemvFp8Desc()
+        d.dtype = L.DT_BF16
+        d.x, d.W, d.ldw, d.scale, d.C, d.N, d.K = x.data_ptr(), codes.data_ptr(), K + 16, scale.data_ptr(), out.data_ptr(), N, K
+        for k, v in kw.items():
+            setattr(d, k, v)
+        return d
+
+    INV = L.E_INVALID
+    cases = [("K % 16", desc(K=K - 8)), ("K % 16 (8)", desc(K=8)), ("N % 4", desc(N=N - 2)), ("null scales", desc(scale=None)),
+             ("null x", desc(x=None)), ("null W", desc(W=None)), ("null C", desc(C=None)), ("ldw % 16", desc(ldw=K + 8)),
+             ("ldw < K", desc(ldw=K - 16)), ("x not 16-byte aligned", desc(x=x.data_ptr() + 2)),
+             ("W not 16-byte aligned", desc(W=codes.data_ptr() + 8)), ("N = 0", desc(N=0)), ("dtype", desc(dtype=7)),
+             ("SwiGLU + bias", desc(act=L.ACT_SWIGLU, bias=x.data_ptr())),
+             ("rope, head_dim % 4", desc(rope_cos=scale.data_ptr(), rope_cols=60, head_dim=30)),
+             ("kv_col0 % 4", desc(kv_k=kv.data_ptr(), kv_v=kv.data_ptr() + 64, kv_col0=30, kv_dim=17)),
+             ("kv rows not the tail", desc(kv_k=kv.data_ptr(), kv_v=kv.data_ptr() + 64, kv_col0=16, kv_dim=16)),
+             ("kv + fp32 out", desc(kv_k=kv.data_ptr(), kv_v=kv.data_ptr() + 64, kv_col0=32, kv_dim=16, out_f32=1))]
+    for name, d in cases:
+        got = L.lib.cogs_gemv_fp8(L.current_stream(), C.byref(d))
+        assert got == INV, (name, got)
+    assert L.lib.cogs_gemv_fp8(L.current_stream(), None) == INV
+    assert L.lib.cogs_quantize_fp8_rows(L.current_stream(), L.DT_BF16, x.data_ptr(), 24, 1, 24, codes.data_ptr(), 24,
+                                        scale.data_ptr(), None, 0) == INV
+    torch.cuda.synchronize()
+    assert torch.equal(_bits(out), before) and torch.equal(_bits(kv), kv_before)
+    assert L.lib.cogs_gemv_fp8(L.current_stream(), C.byref(desc())) == 0          # the base descriptor itself is fine
+    torch.cuda.synchronize()
+    assert torch.equal(out[:N].float().cpu(), torch.zeros(N))
+
+
+# ----------------------------------------------------------------------------------------------------------- 3. device quantiser
+def _check_device_quantiser(dev, w_cpu, dtype):
+    from cogstream_amd import ops
+    from cogstream_amd.weights import dequantize_fp8_rows, quantize_fp8_rows
+    w_cpu = w_cpu.to(dtype)
+    codes_h, scale_h = quantize_fp8_rows(w_cpu)
+    w_dev = w_cpu.to(dev)
+    deq = torch.empty_like(w_dev)
+    codes_d, scale_d = ops.quantize_fp8_rows(w_dev, dequant=deq)
+    assert torch.equal(scale_d.cpu(), scale_h)
+    assert torch.equal(codes_d, codes_h.to(dev)), int((codes_d != codes_h.to(dev)).sum())
+    assert torch.equal(deq.cpu().float(), dequantize_fp8_rows(codes_h, scale_h))
+    codes_p, scale_p = ops.quantize_fp8_rows(w_dev, dequant=w_dev)           # in place, as the load path runs it
+    assert torch.equal(codes_p, codes_d) and torch.equal(scale_p, scale_d) and torch.equal(_bits(w_dev), _bits(deq))
+
+
+@pytest.mark.parametrize("dtype", [BF16, F32], ids=["bf16", "fp32"])
+def test_device_quantiser_is_the_host_quantiser(dev, dtype):
+    for name, w in _inputs():
+        if w.shape[1] % 16:
+            continue
+        _check_device_quantiser(dev, w, dtype)
+    g = torch.Generator().manual_seed(2)
+    w = torch.randn(37, 48, generator=g)
+    w[5] = -0.0
+    w[6, 3] = 2.0 ** -130                                                      # a denormal among ordinary values
+    _check_device_quantiser(dev, w, dtype)
+
+
+def test_device_quantiser_on_the_lm_head(dev):
+    """one 152 064 x 3 584 bf16 matrix: every code and scale equal to the host function's"""
+    torch.set_num_threads(16)
+    g = torch.Generator(device=dev).manual_seed(4)
+    w = (torch.randn(152064, 3584, generator=g, device=dev) * 0.02).to(BF16).cpu()
+    _check_device_quantiser(dev, w, BF16)
+
+
+# ----------------------------------------------------------------------------------------------------------- 4. fp32 engine
+SMALL = dict(hidden_size=256, intermediate_size=512, num_hidden_layers=2, num_attention_heads=2, num_key_value_heads=1,
+             vocab_size=512, image_token_index=500, eos_token_id=499)
+
+
+def test_fp32_engine_vs_oracle_on_the_dequantised_state(dev):
+    """prefill + three cached decode steps in fp32 against the CPU oracle on fp8_model_state: 1e-4 of the maximum, the bar
+    the golden fixture's fp32 logits are asserted at"""
+    from cogstream_amd import _lib as L
+    from cogstream_amd.llm import Qwen2Engine
+    from cogstream_amd.weights import LlmConfig, fp8_model_state, random_llm_state
+    from oracle import qwen2 as oq
+    cfg = LlmConfig(**SMALL)
+    st = random_llm_state(cfg, seed=7, std=0.05)
+    ref_st = fp8_model_state(st)
+    eng = Qwen2Engine(st, cfg, dtype=F32, device=dev, decode_weights="fp8")
+    kw = dict(heads=cfg.num_attention_heads, kv_heads=cfg.num_key_value_heads, layers=cfg.num_hidden_layers)
+    torch.manual_seed(3)
+    emb = torch.randn(21, cfg.hidden_size) * 0.5
+    cache = eng.new_cache(32)
+    r = eng.forward(emb.to(dev), cache)
+    assert L.debug_get("llm_last_decode_fp8") == 0                             # a prompt never reads the codes
+    hid, kv = oq.forward(ref_st, emb, **kw)
+    assert rel_err(r["logits"], oq.logits(ref_st, hid[-1])) < 1e-4
+    for step in range(3):
+        e = torch.randn(1, cfg.hidden_size) * 0.5
+        r = eng.forward(e.to(dev), cache)
+        assert L.debug_get("llm_last_decode_fp8") == 1
+        h1, kv = oq.forward(ref_st, e, past=kv, **kw)
+        err = rel_err(r["logits"], oq.logits(ref_st, h1[-1]))
+        assert err < 1e-4, (step, err)
+    # the original weights are another model: the same bar does not hold against them
+    h0, _ = oq.forward(st, emb, **kw)
+    assert rel_err(eng.forward(emb.to(dev), eng.new_cache(32))["logits"], oq.logits(st, h0[-1])) > 1e-3
+
+
+# ----------------------------------------------------------------------------------------------------------- 5. production width
+def _bf16_step(v):
+    """the bf16 spacing at |v| (8 significant bits)"""
+    return torch.exp2(torch.floor(torch.log2(v.abs().clamp_min(2.0 ** -126))) - 7)
+
+
+def test_bf16_decode_at_production_width(dev):
+    """the setup of test_decode_gemvs_at_production_width_vs_oracle (one layer at Qwen2-7B's widths, a 130-token prompt, three
+    steps) with its own two bars: two summation orders of one model agree to 1e-2, either agrees with the fp32 oracle on
+    that model to 3e-2. The model is fp8_model_state; the other order is the same handle with llm_decode_fp8 = 0."""
+    from cogstream_amd import _lib as L
+    from cogstream_amd.llm import Qwen2Engine
+    from cogstream_amd.weights import LlmConfig, fp8_model_state, random_llm_state
+    from oracle import qwen2 as oq
+    torch.set_num_threads(16)
+    cfg = LlmConfig(num_hidden_layers=1, vocab_size=1024, image_token_index=1000, eos_token_id=999)
+    st = random_llm_state(cfg, seed=11, std=0.02)
+    ref_st = fp8_model_state(st, dtype=BF16)                                   # fp32 tensors holding the bf16 engine's model
+    eng = Qwen2Engine(st, cfg, dtype=BF16, device=dev, decode_weights="fp8")
+    assert eng.packed.fp8_bytes == 1024 * 3584 + (4608 * 3584 + 3584 * 3584 + 2 * 18944 * 3584 + 3584 * 18944)
+    kw = dict(heads=cfg.num_attention_heads, kv_heads=cfg.num_key_value_heads, layers=cfg.num_hidden_layers)
+    torch.manual_seed(12)
+    emb = torch.randn(130, cfg.hidden_size) * 0.5
+    hid, kv = oq.forward(ref_st, emb, **kw)
+    outs, rows = {}, {}
+    for sw in (1, 0):
+        with L.debug_switch("llm_decode_fp8", sw):
+            cache = eng.new_cache(160)
+            eng.forward(emb.to(dev, BF16), cache)
+            torch.manual_seed(13)
+            kv_s, got = kv, []
+            for step in range(3):
+                e = torch.randn(1, cfg.hidden_size) * 0.5
+                r = eng.forward(e.to(dev, BF16), cache)
+                assert L.debug_get("llm_last_decode_fp8") == sw
+                if sw == 0:
+                    assert L.debug_get("gemm_last_body") == 6
+                h1, kv_s = oq.forward(ref_st, e, past=kv_s, **kw)
+                err = rel_err(r["logits"], oq.logits(ref_st, h1[-1]))
+                print(f"decode_fp8={sw} step {step}: rel err vs oracle on the dequantised model {err:.3e}")
+                assert err < 3e-2, (sw, step, err)
+                got.append(r["logits"].float().cpu())
+            outs[sw] = torch.stack(got)
+            rows[sw] = (cache.k[:, 130:133].float().cpu(), cache.v[:, 130:133].float().cpu())
+            if sw == 1:
+                prefill_rows = (cache.k[:, :130].clone(), cache.v[:, :130].clone())
+            else:
+                assert torch.equal(cache.k[:, :130], prefill_rows[0]) and torch.equal(cache.v[:, :130], prefill_rows[1])
+    ab = rel_err(outs[1], outs[0])
+    print(f"fp8 GEMVs vs the dequantised bf16 GEMVs: rel err {ab:.3e}")
+    assert ab < 1e-2, ab
+    for a, b in zip(rows[1], rows[0]):
+        assert bool(((a - b).abs() <= torch.maximum(_bf16_step(a), _bf16_step(b))).all()), float((a - b).abs().max())
+
+
+# ----------------------------------------------------------------------------------------------------------- 6. one model
+@pytest.mark.parametrize("dims", ["small", "wide"])
+def test_prefill_is_bit_identical_to_a_plain_engine_on_the_dequantised_state(dev, dims):
+    from cogstream_amd import _lib as L
+    from cogstream_amd.llm import Qwen2Engine
+    from cogstream_amd.weights import LlmConfig, fp8_model_state, random_llm_state
+    cfg = LlmConfig(**SMALL) if dims == "small" else LlmConfig(hidden_size=1024, intermediate_size=2816, num_hidden_layers=2,
+                                                             num_attention_heads=8, num_key_value_heads=2, vocab_size=2048,
+                                                             image_token_index=2000, eos_token_id=1999)
+    st = random_llm_state(cfg, seed=5, std=0.03)
+    e8 = Qwen2Engine(st, cfg, dtype=BF16, device=dev, decode_weights="fp8")
+    pl = Qwen2Engine(fp8_model_state(st, dtype=BF16), cfg, dtype=BF16, device=dev)
+    assert pl.decode_weights is None and e8.decode_weights == "fp8"
+    torch.manual_seed(6)
+    emb = (torch.randn(77, cfg.hidden_size) * 0.5).to(dev, BF16)
+    a = e8.forward(emb, e8.new_cache(80), want_hidden=True, want_pooled=True)
+    assert L.debug_get("llm_last_decode_fp8") == 0
+    b = pl.forward(emb, pl.new_cache(80), want_hidden=True, want_pooled=True)
+    for k in ("logits", "hidden", "pooled"):
+        assert torch.equal(_bits(a[k]), _bits(b[k])), k
+    seg_a, seg_b = e8.forward_segments(emb, [30, 47]), pl.forward_segments(emb, [30, 47])
+    assert torch.equal(_bits(seg_a), _bits(seg_b))
+    tgt = torch.randint(0, cfg.vocab_size, (77,))
+    sa, sb = e8.score(emb, tgt), pl.score(emb, tgt)
+    assert torch.equal(_bits(sa["logprobs"]), _bits(sb["logprobs"]))
+    # ... and a decode step of the plain engine is a decode step of the fp8 engine with the switch off
+    ca, cb = e8.new_cache(80), pl.new_cache(80)
+    e8.forward(emb, ca), pl.forward(emb, cb)
+    with L.debug_switch("llm_decode_fp8", 0):
+        da = e8.forward(emb[:1], ca)["logits"]
+    db = pl.forward(emb[:1], cb)["logits"]
+    assert torch.equal(_bits(da), _bits(db))
+
+
+# ----------------------------------------------------------------------------------------------------------- 7. product path
+VIT = dict(hidden_size=576, intermediate_size=200, num_hidden_layers=2, num_attention_heads=8)
+TINY = dict(hidden_size=256, intermediate_size=512, num_hidden_layers=2, num_attention_heads=2, num_key_value_heads=1,
+            vocab_size=512, image_token_index=258, eos_token_id=257)
+LLM_SEED = 7            # the plain model on the dequantised weights alone meets the cap below with this seed (see the test)
+STEPS = 32
+
+
+def test_from_pretrained_fp8_generates_and_follows_the_dequantised_model(dev, tmp_path):
+    """A checkpoint directory loaded with decode_weights="fp8" (also through auto.AutoModelForCausalLM): qa_selection ->
+    generate run, the token loop reads the codes, an adapter follows the base model. Then, teacher-forced with the greedy
+    tokens of a plain bf16 engine on fp8_model_state, the fp8 engine's argmax agrees at every step where that engine's
+    top-2 margin exceeds twice the largest logit difference seen; at most 1 step in 8 may fall below that margin."""
+    from golden.inputs import e2e_inputs
+    from toy_tokenizer import ToyTokenizer
+    from cogstream_amd import _lib as L
+    from cogstream_amd import checkpoint as ck
+    from cogstream_amd.auto import AutoModelForCausalLM
+    from cogstream_amd.chat import CogReasoner
+    from cogstream_amd.llm import Qwen2Engine
+    from cogstream_amd.weights import (LlmConfig, VisionConfig, fp8_model_state, random_llm_state, random_lora_state,
+                                       random_proj_state, random_vit_state)
+    vcfg, lcfg = VisionConfig(**VIT), LlmConfig(**TINY)
+    llm_state = random_llm_state(lcfg, seed=LLM_SEED, std=0.05)
+    d = str(tmp_path / "ckpt")
+    ck.save_checkpoint(d, random_vit_state(vcfg, seed=3, std=0.05), random_proj_state(vcfg.hidden_size, lcfg.hidden_size, seed=1, std=0.05),
+                       llm_state, vcfg, lcfg, generation={"do_sample": False, "eos_token_id": [257]}, n_shards=3, dtype=BF16)
+    inp = e2e_inputs("a")
+    tok = ToyTokenizer()
+    enc = tok(inp["text"])
+
+    def answer(model, n=8):
+        sel = model.qa_selection(current_question=inp["current_question"], hist_qs=inp["hist_qs"], hist_as=inp["hist_as"],
+                                 tokenizer=tok, original_text=inp["text"], input_ids=enc["input_ids"],
+                                 attention_mask=enc["attention_mask"], mode="FCC", all_timestamps=inp["timestamps"])
+        ids, _ = model.generate(pixel_values=inp["pixel_values"].bfloat16(), grid_sizes=inp["grid_sizes"], merge_sizes=inp["merge_sizes"],
+                                modals=["video"], new_input_ids=sel["new_input_ids"], new_attention_mask=sel["new_attention_mask"],
+                                selection_module_output=sel["selection_module_output"], if_visual=sel["if_visual"],
+                                total_image_num=inp["T"], max_new_tokens=n, do_sample=False, eos_token_id=[-1])
+        return ids[0].tolist()
+
+    plain = CogReasoner.from_pretrained(d, torch_dtype=BF16, device=dev)
+    assert plain.llm.decode_weights is None and plain.llm.packed.fp8_bytes == 0
+    assert len(answer(plain)) == 8
+    assert L.debug_get("llm_last_decode_fp8") == 0 and L.debug_get("gemm_last_body") == 6
+    model = AutoModelForCausalLM.from_pretrained(d, trust_remote_code=True, torch_dtype=BF16, device=dev, decode_weights="fp8")
+    assert isinstance(model, CogReasoner) and model.llm.decode_weights == "fp8"
+    H, I, V, nl = lcfg.hidden_size, lcfg.intermediate_size, lcfg.vocab_size, lcfg.num_hidden_layers
+    qd = (lcfg.num_attention_heads + 2 * lcfg.num_key_value_heads) * lcfg.head_dim
+    assert model.llm.packed.fp8_bytes == V * H + nl * (qd * H + H * H + 2 * I * H + H * I)
+    toks = answer(model)
+    assert len(toks) == 8 and all(0 <= t < V for t in toks)
+    assert L.debug_get("llm_last_decode_fp8") == 1
+    # what from_pretrained streamed and quantised on the device is the host's quantisation of the same tensors
+    from cogstream_amd.weights import PackedLlm
+    ref_pack = PackedLlm({k: v.to(BF16) for k, v in llm_state.items()}, lcfg, dtype=BF16, device="cpu", decode_weights="fp8")
+    for k, c in ref_pack.fp8_codes.items():
+        assert torch.equal(model.llm.packed.fp8_codes[k].cpu(), c), k
+        assert torch.equal(model.llm.packed.fp8_scales[k].cpu(), ref_pack.fp8_scales[k]), k
+    # an adapter follows the base model: merged first, quantised after
+    lora = random_lora_state(lcfg, r=4, proj_dims=(vcfg.hidden_size, lcfg.hidden_size))
+    model.load_adapter({k: v.to(dev, BF16) for k, v in llm_state.items()}, None, lora, "full_module", lora_alpha=8.0)
+    assert model._adapters["full_module"][0].decode_weights == "fp8"
+    plain.load_adapter({k: v.to(dev, BF16) for k, v in llm_state.items()}, None, lora, "full_module", lora_alpha=8.0)
+    assert plain._adapters["full_module"][0].decode_weights is None
+
+    # teacher forcing
+    e8 = model.llm
+    pl = Qwen2Engine(fp8_model_state({k: v.to(BF16) for k, v in llm_state.items()}), lcfg, dtype=BF16, device=dev)
+    prompt = e8.embed_tokens(enc["input_ids"].reshape(-1))
+    c8, cp = e8.new_cache(prompt.shape[0] + STEPS + 1), pl.new_cache(prompt.shape[0] + STEPS + 1)
+    l8, lp = e8.forward(prompt, c8)["logits"], pl.forward(prompt, cp)["logits"]
+    assert torch.equal(_bits(l8), _bits(lp))                                    # one model: the prompt pass is the same bits
+    diffs, margins, agree = [], [], []
+    for step in range(STEPS):
+        t = int(lp.argmax())
+        e = pl.embed_tokens(torch.tensor([t]))
+        lp = pl.forward(e, cp)["logits"]
+        l8 = e8.forward(e, c8)["logits"]
+        assert L.debug_get("llm_last_decode_fp8") == 1
+        top2 = torch.topk(lp, 2).values
+        diffs.append(float((l8 - lp).abs().max()))
+        margins.append(float(top2[0] - top2[1]))
+        agree.append(int(l8.argmax()) == int(lp.argmax()))
+    worst = max(diffs)
+    exempt = [m <= 2 * worst for m in margins]
+    print(f"teacher forcing, {STEPS} steps: largest logit difference {worst:.4g}, smallest margin {min(margins):.4g}, "
+          f"steps below 2 x difference {sum(exempt)}, disagreements {agree.count(False)}")
+    assert all(a for a, x in zip(agree, exempt) if not x), (diffs, margins, agree)
+    assert sum(exempt) * 8 <= STEPS, (sum(exempt), worst, sorted(margins)[:6])
