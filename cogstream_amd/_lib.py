@@ -146,6 +146,23 @@ class KV(C.Structure):
     _fields_ = [("k", c_void_p), ("v", c_void_p), ("max_len", c_int), ("len", c_int)]
 
 
+class AttnRowsDesc(C.Structure):
+    _fields_ = [
+        ("dtype", c_int),
+        ("Q", c_void_p), ("ldq", c_int64),
+        ("K", c_void_p), ("V", c_void_p), ("ldk", c_int64), ("ldv", c_int64), ("prefix_len", c_int),
+        ("tail_k", c_void_p), ("tail_v", c_void_p), ("tail_ld", c_int64), ("tail_row_stride", c_int64), ("tail_len", c_int),
+        ("O", c_void_p),
+        ("rows", c_int), ("hq", c_int), ("hkv", c_int), ("head_dim", c_int),
+        ("nsplit", c_int), ("ws", c_void_p), ("ws_bytes", c_size_t),
+    ]
+
+
+class KVRows(C.Structure):
+    _fields_ = [("k", c_void_p), ("v", c_void_p), ("max_len", c_int), ("prefix_len", c_int),
+                ("tail_k", c_void_p), ("tail_v", c_void_p), ("tail_max", c_int), ("tail_len", c_int)]
+
+
 # every symbol include/cogs.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "cogs_status_string": (C.c_char_p, [c_int]),
@@ -159,6 +176,10 @@ SIGNATURES = {
     "cogs_profile_begin": (c_int, [c_void_p]),
     "cogs_profile_end": (c_int, [c_void_p, c_void_p, C.POINTER(c_float), C.POINTER(c_int)]),
     "cogs_gemm": (c_int, [c_void_p, C.POINTER(GemmDesc)]),
+    "cogs_gemm_rows": (c_int, [c_void_p, C.POINTER(GemmDesc), c_float, c_int]),
+    "cogs_attention_rows": (c_int, [c_void_p, C.POINTER(AttnRowsDesc)]),
+    "cogs_llm_decode_rows_workspace_bytes": (c_int, [c_void_p, c_int, c_int, C.POINTER(c_size_t)]),
+    "cogs_llm_decode_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int, C.POINTER(KVRows), c_void_p, c_void_p, c_size_t]),
     "cogs_gemv_fp8": (c_int, [c_void_p, C.POINTER(GemvFp8Desc)]),
     "cogs_quantize_fp8_rows": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p,
                                        c_int64]),

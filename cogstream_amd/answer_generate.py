@@ -32,9 +32,10 @@ from .chat import parse_selection
 
 @torch.inference_mode()
 def infer(conversation, model, processor, select=None, if_visual=None, max_new_tokens: int = 1024,
-          score_answer: Optional[str] = None, **gen_kwargs):
+          score_answer: Optional[str] = None, responses_out: Optional[list] = None, **gen_kwargs):
     """evaluate/answer_generate.py:60-76 -> (response, selection); with `score_answer` (a ground-truth answer) a third
-    element: model.score_answers' dict for that answer under the same prompt"""
+    element: model.score_answers' dict for that answer under the same prompt. With num_return_sequences=N among the
+    generation keywords the response is row 0 and `responses_out` (a list) receives all N decoded rows."""
     inputs = processor(conversation=conversation, add_system_prompt=True, add_generation_prompt=True, return_tensors="pt")
     inputs = {k: (v.to(model.device) if isinstance(v, torch.Tensor) and k in ("pixel_values",) else v) for k, v in inputs.items()}
     if "pixel_values" in inputs and model.dtype == torch.bfloat16:
@@ -48,7 +49,10 @@ def infer(conversation, model, processor, select=None, if_visual=None, max_new_t
     if "full_module" in has:
         model.set_adapter("full_module")
     output_ids, selection = model.generate(**inputs, max_new_tokens=max_new_tokens, **gen_kwargs)
-    response = processor.batch_decode(output_ids, skip_special_tokens=True)[0].strip()
+    decoded = processor.batch_decode(output_ids, skip_special_tokens=True)
+    response = decoded[0].strip()
+    if responses_out is not None:
+        responses_out[:] = [d.strip() for d in decoded]
     if score_answer is not None:
         return response, selection, model.score_answers(**inputs, answers=[score_answer])[0]
     return response, selection
@@ -80,11 +84,13 @@ def run_session(model, processor, segments: Sequence[Dict[str, Any]], system: st
                 conversation.append({"role": "user", "content": q})
             gt = seg.get("answers", [None] * len(seg["questions"]))[i]
             score = None
+            many = [] if int(gen_kwargs.get("num_return_sequences", 1) or 1) > 1 else None
             if score_answers and gt is not None:
                 out, selection, score = infer(conversation, model, processor, max_new_tokens=max_new_tokens,
-                                              score_answer=gt, **gen_kwargs)
+                                              score_answer=gt, responses_out=many, **gen_kwargs)
             else:
-                out, selection = infer(conversation, model, processor, max_new_tokens=max_new_tokens, **gen_kwargs)
+                out, selection = infer(conversation, model, processor, max_new_tokens=max_new_tokens, responses_out=many,
+                                       **gen_kwargs)
             if hist > 0:
                 vis, idx = parse_selection(selection)
                 relevance = [1 if j in idx else 0 for j in range(hist)]
@@ -94,6 +100,8 @@ def run_session(model, processor, segments: Sequence[Dict[str, Any]], system: st
                             "predicted_visual": vis, "coi": (seg.get("relevance") or [None] * len(seg["questions"]))[i]})
             if score is not None:
                 _add_answer_score(records[-1], score)
+            if many is not None:
+                records[-1]["responses"] = list(many)
             hist += 1
             conversation.append({"role": "assistant", "content": out})
     return records
@@ -199,11 +207,13 @@ def answer_video(model, processor, video_path: str, query_chain, max_new_tokens:
         for i, qa in enumerate(qas):
             conversation.append(cov if i == 0 else {"role": "user", "content": _scalar(qa["Q"])})
             score = None
+            many = [] if int(gen_kwargs.get("num_return_sequences", 1) or 1) > 1 else None
             if score_answers:
                 output, selection, score = infer(conversation, model, processor, max_new_tokens=max_new_tokens,
-                                                 score_answer=str(_scalar(qa["A"])), **gen_kwargs)
+                                                 score_answer=str(_scalar(qa["A"])), responses_out=many, **gen_kwargs)
             else:
-                output, selection = infer(conversation, model, processor, max_new_tokens=max_new_tokens, **gen_kwargs)
+                output, selection = infer(conversation, model, processor, max_new_tokens=max_new_tokens, responses_out=many,
+                                          **gen_kwargs)
             if hist > 0:
                 vis, idx = parse_selection(selection)
                 relevance = [1 if j in idx else 0 for j in range(hist)]
@@ -214,6 +224,8 @@ def answer_video(model, processor, video_path: str, query_chain, max_new_tokens:
                                  "coi": qa["info"]["relevance"]})      # the file's own value (the reference's [0] undoes the collate)
             if score is not None:
                 _add_answer_score(video_answer[-1], score)
+            if many is not None:       # beside the unchanged `prediction` (= row 0, which also continues the conversation)
+                video_answer[-1]["responses"] = list(many)
             hist += 1
             conversation.append({"role": "assistant", "content": output})
     return [video_answer]
@@ -272,7 +284,12 @@ def main(argv=None) -> int:
                     help="add answer_logprob / answer_ppl of the ground-truth answer to every result record")
     ap.add_argument("--decode-weights", dest="decode_weights", choices=["bf16", "fp8"], default="bf16",
                     help="fp8: W8A16 decode -- the token loop streams e4m3 codes of the Qwen2 linears (half the weight bytes)")
+    ap.add_argument("--num_return_sequences", type=int, default=1,
+                    help="N > 1: N sampled answers per question from one prefill (lockstep decode); every record gets a `responses` "
+                         "list beside `prediction` (= the first of them)")
     args = ap.parse_args(argv)
+    if args.num_return_sequences > 1 and args.greedy:
+        ap.error("--num_return_sequences needs sampling (drop --greedy)")
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -292,6 +309,8 @@ def main(argv=None) -> int:
     model.to(dev)
     dataset = VideoDataset(args.video_dir, args.query_dir)
     gen = {"do_sample": False} if args.greedy else {}
+    if args.num_return_sequences > 1:
+        gen["num_return_sequences"] = args.num_return_sequences
     if shard:
         model.enable_sharded_encoder(rank, world, payload=args.payload)
         if args.spread_events:

@@ -666,7 +666,9 @@ class CogReasoner:
     @torch.no_grad()
     def generate(self, pixel_values=None, grid_sizes=None, merge_sizes=None, modals=None, new_input_ids=None,
                  new_attention_mask=None, selection_module_output="", if_visual=True, video_keys=None, **kwargs):
-        """:753-807 -> (new token ids [1, n], selection_module_output)"""
+        """:753-807 -> (new token ids [1, n], selection_module_output). num_return_sequences = N > 1 (forwarded to
+        GenerationMixin.generate by the reference's **kwargs, :802-807): [N, L] int64, rows that stopped early right-padded
+        with the generation config's pad_token_id (or the keyword's), as transformers returns them."""
         for k in ("input_ids", "past_key_values", "attention_mask", "position_ids", "tokenizer", "hist_qs", "hist_as",
                   "current_question", "original_text"):
             kwargs.pop(k, None)
@@ -684,6 +686,8 @@ class CogReasoner:
             embeds = self.llm.embed_tokens(new_input_ids.reshape(-1))
         if helper:     # frame-sharded run: the llm_rank prefills and decodes; its new token ids arrive by broadcast
             got = self._bcast(None)
+            if got and isinstance(got[0], (list, tuple)):       # num_return_sequences > 1: the padded rows
+                return torch.tensor(got, dtype=torch.int64), selection_module_output
             return torch.tensor(got, dtype=torch.int64).reshape(1, len(got)), selection_module_output
         g = dict(self.generation_config)
         g.update({k: v for k, v in kwargs.items() if k in ("do_sample", "temperature", "top_k", "top_p",
@@ -697,7 +701,19 @@ class CogReasoner:
                                 top_k=int(g.get("top_k", 0) or 0), top_p=float(g.get("top_p", 1.0)),
                                 repetition_penalty=float(g.get("repetition_penalty", 1.0)), generator=g.get("generator"),
                                 sampler=g.get("sampler", "device"), seed=g.get("seed"),
-                                prefix=self._prefix_slot("answer"))
+                                prefix=self._prefix_slot("answer"),
+                                num_return_sequences=int(kwargs.get("num_return_sequences", g.get("num_return_sequences", 1)) or 1))
+        if new and isinstance(new[0], list):                    # N rows
+            from .llm import pad_rows
+            pad = kwargs.get("pad_token_id", g.get("pad_token_id"))
+            if pad is None:
+                if any(len(r) != len(new[0]) for r in new):
+                    raise ValueError("rows of different lengths need a pad_token_id (generation config or keyword)")
+                pad = 0
+            out = pad_rows(new, int(pad))
+            if self._shard is not None:
+                self._bcast(out.tolist())
+            return out, selection_module_output
         if self._shard is not None:
             self._bcast(list(new))
         return torch.tensor(new, dtype=torch.int64).unsqueeze(0), selection_module_output

@@ -1181,3 +1181,26 @@ int cogs_k_attention(hipStream_t st, const CogsAttn& a) {
         hipLaunchKernelGGL(attn_rowwise_kernel<float>, grid, dim3(64), 0, st, p, a.head_dim, nseg);
     return COGS_LAUNCH_CHECK();
 }
+
+int cogs_k_attention_combine(hipStream_t st, const float* part_o, const float* part_ml, int nparts, int heads, int head_dim,
+                             void* O) {
+    if (nparts < 1 || nparts > 128 || heads < 1 || head_dim < 1 || head_dim > 256) return COGS_E_INVALID;
+    if (head_dim % 32 == 0 && g_cogs_debug.attn_combine32)
+        hipLaunchKernelGGL(attn_combine32_kernel, dim3(1, heads, head_dim / 32), dim3(256), 0, st, part_o, part_ml, nparts, 1, heads,
+                           head_dim, (bf16_t*)O, (long)heads * head_dim);
+    else
+        hipLaunchKernelGGL(attn_combine_kernel, dim3(1, heads), dim3(256), 0, st, part_o, part_ml, nparts, 1, heads, head_dim,
+                           (bf16_t*)O, (long)heads * head_dim);
+    return COGS_LAUNCH_CHECK();
+}
+
+int cogs_k_attention_rows(hipStream_t st, const CogsAttnRows& a) {
+    if (a.nsplit < 1 || a.nsplit > 127) return COGS_E_INVALID;
+    const size_t slots = (size_t)(a.nsplit + 1) * a.rows * a.hq;
+    if (!a.ws || a.ws_bytes < slots * (a.head_dim + 2) * sizeof(float)) return COGS_E_WORKSPACE;
+    float* part_o = (float*)a.ws;
+    float* part_ml = part_o + slots * a.head_dim;
+    const int rc = cogs_k_attention_decode_rows(st, a, part_o, part_ml);
+    if (rc != COGS_OK) return rc;
+    return cogs_k_attention_combine(st, part_o, part_ml, a.nsplit + 1, a.rows * a.hq, a.head_dim, a.O);
+}

@@ -31,6 +31,10 @@ struct DecodeAttnArgs {
     int hq, hkv, nsplit, gsz;
     float* part_o;                 // [nsplit][hq][128] unnormalised, relative to part_ml[..][0]
     float* part_ml;                // [nsplit][hq][2] (running max in log2 units, sum)
+    // multi-row form (ROWS): `rows` query rows share keys [0, kend) of K / V and own keys [0, tail_len) of tail_k / tail_v[row]
+    const bf16_t* tail_k; const bf16_t* tail_v;
+    long ldq, tail_ld, tail_row;   // elements: Q row stride, tail key stride, tail stride between rows
+    int rows, ntile, tail_len;     // ntile = ceil(rows * gsz / 16) column tiles per kv head
 };
 
 // max / sum over the four lanes {li, li+16, li+32, li+48} (one query column), result in all four (see attn.hip)
@@ -48,6 +52,11 @@ __device__ __forceinline__ float col_sum4(float x) {
     return x;
 }
 
+// ROWS (cogs_attention_rows): the rows * gsz query columns of a kv head are packed into ntile tiles of 16 -- column c is head
+// c % gsz of row c / gsz, a row's heads may straddle two tiles -- and workgroup x < nsplit * ntile runs split x % nsplit of
+// the shared keys for tile x / nsplit; workgroup nsplit * ntile + r runs row r's own tail as ONE more partial (index nsplit)
+// of that row's gsz columns. Partials are [nsplit + 1][rows * hq] slots: the combine kernel sees rows * hq heads.
+template <bool ROWS>
 __global__ __launch_bounds__(256, 1) void attn_decode_kernel(DecodeAttnArgs p) {
     constexpr int HD = 128, VRS = 288, VT = 64 * VRS;
     __shared__ __attribute__((aligned(16))) char vs[4 * VT];          // one V tile per wave
@@ -57,21 +66,44 @@ __global__ __launch_bounds__(256, 1) void attn_decode_kernel(DecodeAttnArgs p) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, g = lane >> 4;
-    const int split = blockIdx.x, kvh = blockIdx.y;
+    const int kvh = blockIdx.y;
     const int gsz = p.gsz;                                       // hq / hkv, divided on the host
+    int split = blockIdx.x, nsplit = p.nsplit, kend = p.kend, ncols = gsz, part = blockIdx.x;
+    const bf16_t* Kp = p.K; const bf16_t* Vp = p.V;
+    long ldk = p.ldk, ldv = p.ldv;
+    long qoff = (long)(kvh * gsz + li) * HD;                     // this lane's query column: element offset in Q ...
+    int oslot = kvh * gsz + li;                                  // ... and its (row, head) slot inside one partial
+    if constexpr (ROWS) {
+        const int shared_blocks = p.nsplit * p.ntile;
+        if ((int)blockIdx.x < shared_blocks) {
+            split = blockIdx.x % p.nsplit; part = split;
+            const int c0 = 16 * (int)(blockIdx.x / p.nsplit);
+            ncols = min(16, p.rows * gsz - c0);
+            const int row = (c0 + li) / gsz, hh = (c0 + li) - row * gsz;
+            qoff = (long)row * p.ldq + (long)(kvh * gsz + hh) * HD;
+            oslot = row * p.hq + kvh * gsz + hh;
+        } else {
+            const int row = blockIdx.x - shared_blocks;
+            split = 0; nsplit = 1; part = p.nsplit; kend = p.tail_len;
+            Kp = p.tail_k + (long)row * p.tail_row; Vp = p.tail_v + (long)row * p.tail_row;
+            ldk = ldv = p.tail_ld;
+            qoff = (long)row * p.ldq + (long)(kvh * gsz + li) * HD;
+            oslot = row * p.hq + kvh * gsz + li;
+        }
+    }
 
     // (unsigned 32-bit: tiles x splits is far below 2^32, checked by the launcher; the signed 64-bit form was two ~100-instruction
     // divisions at the head of a 10 us kernel)
-    const unsigned nt_all = (unsigned)(p.kend + 63) >> 6;
-    const int t_begin = (int)(nt_all * (unsigned)split / (unsigned)p.nsplit);
-    const int t_end = (int)(nt_all * (unsigned)(split + 1) / (unsigned)p.nsplit);
+    const unsigned nt_all = (unsigned)(kend + 63) >> 6;
+    const int t_begin = (int)(nt_all * (unsigned)split / (unsigned)nsplit);
+    const int t_end = (int)(nt_all * (unsigned)(split + 1) / (unsigned)nsplit);
 
     // Q fragments (B operand of S^T = K.Q^T): lane (q = li, g) holds Q[head kvh*gsz + li][32s + 8g .. +7]
     bf16x8 qf[4];
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
         u32x4 v = {0, 0, 0, 0};
-        if (li < gsz) v = *reinterpret_cast<const u32x4*>(p.Q + (long)(kvh * gsz + li) * HD + 32 * s + 8 * g);
+        if (li < ncols) v = *reinterpret_cast<const u32x4*>(p.Q + qoff + 32 * s + 8 * g);
         qf[s] = __builtin_bit_cast(bf16x8, v);
     }
 
@@ -86,22 +118,22 @@ __global__ __launch_bounds__(256, 1) void attn_decode_kernel(DecodeAttnArgs p) {
 
     for (int kt = t_begin + wid; kt < t_end; kt += 4) {
         const int kbase = kt * 64;
-        const int nvalid = min(64, p.kend - kbase);                                // >= 1
-        const bf16_t* kb = p.K + (long)kbase * p.ldk + kvh * HD;
-        const bf16_t* vb = p.V + (long)kbase * p.ldv + kvh * HD;
+        const int nvalid = min(64, kend - kbase);                                  // >= 1
+        const bf16_t* kb = Kp + (long)kbase * ldk + kvh * HD;
+        const bf16_t* vb = Vp + (long)kbase * ldv + kvh * HD;
         // every byte is read once per token by this wave: non-temporal. Rows past the end repeat the last row
         // (finite data; their scores are masked)
         u32x4 kf[4][4], vreg[16];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            const long ro = (long)min(16 * u + li, nvalid - 1) * p.ldk;
+            const long ro = (long)min(16 * u + li, nvalid - 1) * ldk;
 #pragma unroll
             for (int s = 0; s < 4; ++s)
                 kf[u][s] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(kb + ro + 32 * s + 8 * g));
         }
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            const long ro = (long)min((lane >> 4) + 4 * i, nvalid - 1) * p.ldv;
+            const long ro = (long)min((lane >> 4) + 4 * i, nvalid - 1) * ldv;
             vreg[i] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(vb + ro + (lane & 15) * 8));
         }
         // S^T, four key blocks of 16
@@ -164,12 +196,14 @@ __global__ __launch_bounds__(256, 1) void attn_decode_kernel(DecodeAttnArgs p) {
     // merge the four waves: (m, l, O) per query column through LDS
     l = col_sum4(l);
     if (g == 0) { cm[wid][li] = m; cl[wid][li] = l; }
-    if (li < gsz) {
+    __shared__ int cslot[16];
+    if constexpr (ROWS) { if (lane == li && wid == 0) cslot[li] = oslot; }
+    if (li < ncols) {
 #pragma unroll
         for (int db = 0; db < 8; ++db) *reinterpret_cast<f32x4*>(&co[wid][li][16 * db + 4 * g]) = oacc[db];
     }
     __syncthreads();
-    for (int idx = tid; idx < gsz * HD; idx += 256) {
+    for (int idx = tid; idx < ncols * HD; idx += 256) {
         const int q = idx / HD, d = idx % HD;
         const float M = fmaxf(fmaxf(cm[0][q], cm[1][q]), fmaxf(cm[2][q], cm[3][q]));
         float o = 0.f, L = 0.f;
@@ -179,7 +213,8 @@ __global__ __launch_bounds__(256, 1) void attn_decode_kernel(DecodeAttnArgs p) {
             o += co[w][q][d] * wt;
             L += cl[w][q] * wt;
         }
-        const long slot = (long)split * p.hq + kvh * gsz + q;
+        long slot = (long)split * p.hq + kvh * gsz + q;
+        if constexpr (ROWS) slot = (long)part * p.rows * p.hq + cslot[q];
         p.part_o[slot * HD + d] = (M == -INFINITY) ? 0.f : o;
         if (d == 0) { p.part_ml[slot * 2] = M; p.part_ml[slot * 2 + 1] = L; }
     }
@@ -200,6 +235,27 @@ int cogs_k_attention_decode(hipStream_t st, const CogsAttn& a, float* part_o, fl
     p.hq = a.hq; p.hkv = a.hkv; p.nsplit = a.nsplit; p.gsz = a.hq / a.hkv;
     if ((long)((p.kend + 63) >> 6) * (a.nsplit + 1) > 0x7fffffffL) return COGS_E_INVALID;
     p.part_o = part_o; p.part_ml = part_ml;
-    hipLaunchKernelGGL(attn_decode_kernel, dim3(a.nsplit, a.hkv), dim3(256), 0, st, p);
+    p.tail_k = p.tail_v = nullptr; p.ldq = p.tail_ld = p.tail_row = 0; p.rows = 1; p.ntile = 1; p.tail_len = 0;
+    hipLaunchKernelGGL(attn_decode_kernel<false>, dim3(a.nsplit, a.hkv), dim3(256), 0, st, p);
+    return COGS_LAUNCH_CHECK();
+}
+
+// `rows` query rows in lockstep over one shared prompt (cogs_attention_rows, include/cogs.h): key-split partials of the shared
+// keys + one partial per row for its own tail, part_o / part_ml sized for nsplit + 1 partials of rows * hq heads
+int cogs_k_attention_decode_rows(hipStream_t st, const CogsAttnRows& a, float* part_o, float* part_ml) {
+    if (a.head_dim != 128 || a.hkv < 1 || a.hq % a.hkv || a.hq / a.hkv > 16 || a.rows < 1 || a.rows > 16) return COGS_E_UNSUPPORTED;
+    if (a.nsplit < 1 || a.prefix_len < 1 || a.tail_len < 1) return COGS_E_INVALID;
+    if (a.ldk % 8 || a.ldv % 8 || a.ldq % 8 || a.tail_ld % 8 || a.tail_row % 8) return COGS_E_INVALID;
+    DecodeAttnArgs p;
+    p.Q = (const bf16_t*)a.Q; p.K = (const bf16_t*)a.K; p.V = (const bf16_t*)a.V;
+    p.ldk = a.ldk; p.ldv = a.ldv;
+    p.kend = a.prefix_len;
+    p.hq = a.hq; p.hkv = a.hkv; p.nsplit = a.nsplit; p.gsz = a.hq / a.hkv;
+    if ((long)((p.kend + 63) >> 6) * (a.nsplit + 1) > 0x7fffffffL) return COGS_E_INVALID;
+    p.part_o = part_o; p.part_ml = part_ml;
+    p.tail_k = (const bf16_t*)a.tail_k; p.tail_v = (const bf16_t*)a.tail_v;
+    p.ldq = a.ldq; p.tail_ld = a.tail_ld; p.tail_row = a.tail_row;
+    p.rows = a.rows; p.ntile = (a.rows * p.gsz + 15) / 16; p.tail_len = a.tail_len;
+    hipLaunchKernelGGL(attn_decode_kernel<true>, dim3(a.nsplit * p.ntile + a.rows, a.hkv), dim3(256), 0, st, p);
     return COGS_LAUNCH_CHECK();
 }

@@ -277,6 +277,24 @@ cogs_status cogs_gemm(cogs_stream stream, const cogs_gemm_desc* d) {
     return cogs_k_gemm((hipStream_t)stream, to_gemm(d));
 }
 
+cogs_status cogs_gemm_rows(cogs_stream stream, const cogs_gemm_desc* d, float q_scale, int q_cols) {
+    if (!d || !d->A || !d->W || !d->C) return COGS_E_INVALID;
+    CogsGemm g = to_gemm(d);
+    if (q_scale != 0.f) { g.q_scale = q_scale; g.q_cols = q_cols; }
+    return cogs_k_gemm_rows((hipStream_t)stream, g);
+}
+
+cogs_status cogs_attention_rows(cogs_stream stream, const cogs_attn_rows_desc* d) {
+    if (!d || !d->Q || !d->K || !d->V || !d->tail_k || !d->tail_v || !d->O) return COGS_E_INVALID;
+    if (d->dtype != COGS_DT_BF16) return COGS_E_UNSUPPORTED;
+    CogsAttnRows a;
+    a.Q = d->Q; a.ldq = d->ldq; a.K = d->K; a.V = d->V; a.ldk = d->ldk; a.ldv = d->ldv; a.prefix_len = d->prefix_len;
+    a.tail_k = d->tail_k; a.tail_v = d->tail_v; a.tail_ld = d->tail_ld; a.tail_row = d->tail_row_stride; a.tail_len = d->tail_len;
+    a.O = d->O; a.rows = d->rows; a.hq = d->hq; a.hkv = d->hkv; a.head_dim = d->head_dim;
+    a.nsplit = d->nsplit > 1 ? d->nsplit : 1; a.ws = d->ws; a.ws_bytes = d->ws_bytes;
+    return cogs_k_attention_rows((hipStream_t)stream, a);
+}
+
 cogs_status cogs_gemv_fp8(cogs_stream stream, const cogs_gemv_fp8_desc* d) {
     if (!d || !d->x || !d->W || !d->scale || !d->C) return COGS_E_INVALID;
     CogsGemm g;
@@ -1268,6 +1286,121 @@ cogs_status cogs_llm_forward_segments(cogs_handle h, cogs_stream stream, const v
     if (nseg <= 0 || !cu_seqlens_host || !pooled_means) return COGS_E_INVALID;
     return llm_forward_impl(h, stream, embeds, S, nullptr, nullptr, nullptr, nullptr, ws, ws_bytes, cu_seqlens_host, nseg,
                             pooled_means);
+}
+
+// ---- lockstep decode of R continuations of one prompt
+
+static int rows_nsplit(int prefix_len) {       // the single-row split rule; the rows' tails are one more partial (<= 128 in all)
+    const int n = llm_nsplit(prefix_len);
+    return n > 127 ? 127 : n;
+}
+
+static size_t rows_carve(const cogs_llm_weights& w, int R, int max_prefix, Carver& c, void** x, void** ln, void** qkv, void** att,
+                         void** act, float** rc, int32_t** pos, void** split, size_t* split_bytes) {
+    const size_t es = esize(w.dtype);
+    const int qd = (w.heads + 2 * w.kv_heads) * w.head_dim;
+    *x = c.take((size_t)R * w.hidden * es);
+    *ln = c.take((size_t)R * w.hidden * es);
+    *qkv = c.take((size_t)R * qd * es);
+    *att = c.take((size_t)R * w.heads * w.head_dim * es);
+    *act = c.take((size_t)R * w.inter * es);
+    *rc = (float*)c.take((size_t)R * (w.head_dim / 2) * 2 * sizeof(float));
+    *pos = (int32_t*)c.take((size_t)R * sizeof(int32_t));
+    *split_bytes = (size_t)(rows_nsplit(max_prefix) + 1) * R * w.heads * (w.head_dim + 2) * sizeof(float);
+    *split = c.take(*split_bytes);
+    return c.off;
+}
+
+cogs_status cogs_llm_decode_rows_workspace_bytes(cogs_handle h, int R, int max_prefix, size_t* bytes) {
+    if (!h || !h->llm_ok || !bytes || R <= 0 || max_prefix <= 0) return COGS_E_INVALID;
+    Carver c(nullptr, 0);
+    void *a, *b, *d, *e, *f, *sp; float* rc; int32_t* pos; size_t sb;
+    *bytes = rows_carve(h->llm, R, max_prefix, c, &a, &b, &d, &e, &f, &rc, &pos, &sp, &sb);
+    return COGS_OK;
+}
+
+cogs_status cogs_llm_decode_rows(cogs_handle h, cogs_stream stream, const void* embeds, int R, cogs_kv_rows* kv, float* logits,
+                                 void* ws, size_t ws_bytes) {
+    if (!h || !h->llm_ok || !embeds || !kv || !logits || R <= 0) return COGS_E_INVALID;
+    const cogs_llm_weights& w = h->llm;
+    if (w.dtype != COGS_DT_BF16 || w.head_dim != 128 || R > 16) return COGS_E_UNSUPPORTED;
+    if (!kv->k || !kv->v || !kv->tail_k || !kv->tail_v || kv->prefix_len < 1 || kv->prefix_len > kv->max_len || kv->tail_len < 0 ||
+        kv->tail_len >= kv->tail_max)
+        return COGS_E_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    const int dt = w.dtype;
+    const size_t es = esize(dt);
+    const int H = w.hidden, hd = w.head_dim, kvd = w.kv_heads * hd, qd_q = w.heads * hd, qd = qd_q + 2 * kvd;
+    Carver c(ws, ws_bytes);
+    void *x, *ln, *qkv, *att, *act, *split; float* rc; int32_t* pos_d; size_t split_bytes;
+    const size_t need = rows_carve(w, R, kv->prefix_len, c, &x, &ln, &qkv, &att, &act, &rc, &pos_d, &split, &split_bytes);
+    if (!ws || ws_bytes < need) return COGS_E_WORKSPACE;
+    // the e4m3 codes serve single-row steps only: this step reads the (dequantised) matrices of cogs_llm_weights
+    g_cogs_debug.llm_last_decode_fp8 = 0;
+    const int tl = kv->tail_len, position = kv->prefix_len + tl;      // lockstep: one position, one rotary row for every row
+    if (hipMemcpyAsync(x, embeds, (size_t)R * H * es, hipMemcpyDeviceToDevice, st) != hipSuccess) return COGS_E_HIP;
+    if (hipMemsetD32Async((hipDeviceptr_t)pos_d, position, R, st) != hipSuccess) return COGS_E_HIP;
+    { PROF(COGS_PROF_OTHER); COGS_TRY(cogs_k_llm_rope_table(st, rc, nullptr, pos_d, 0, R, h->llm_inv_freq, hd / 2)); }
+    const float scale = 1.0f / sqrtf((float)hd);
+    const int nsplit = rows_nsplit(kv->prefix_len);
+    const size_t tail_row = (size_t)kv->tail_max * kvd;               // elements between two rows' tails
+    for (int l = 0; l < w.layers; ++l) {
+        const cogs_llm_layer& L = h->llm_layers[l];
+        { PROF(COGS_PROF_NORM); COGS_TRY(cogs_k_rmsnorm(st, dt, x, ln, L.in_ln, R, H, w.rms_eps)); }
+        {
+            CogsGemm g; g.dtype = dt;
+            g.A = ln; g.lda = H; g.W = L.qkv_w; g.ldw = H; g.C = qkv; g.ldc = qd;
+            g.bias = L.qkv_b; g.M = R; g.N = qd; g.K = H;
+            g.rope_cos = rc; g.rope_sin = nullptr; g.rope_cols = qd_q + kvd; g.head_dim = hd;
+            g.q_scale = scale * 1.4426950408889634f; g.q_cols = qd_q;
+            { PROF(COGS_PROF_GEMM); COGS_TRY(cogs_k_gemm_rows(st, g)); }
+        }
+        char* tk = (char*)kv->tail_k + (size_t)l * R * tail_row * es;
+        char* tv = (char*)kv->tail_v + (size_t)l * R * tail_row * es;
+        {
+            PROF(COGS_PROF_OTHER);
+            COGS_TRY(cogs_k_kv_append(st, dt, (const char*)qkv + (size_t)qd_q * es, (const char*)qkv + (size_t)(qd_q + kvd) * es, qd,
+                                      tk + (size_t)tl * kvd * es, tv + (size_t)tl * kvd * es, (long)tail_row, R, kvd));
+        }
+        {
+            CogsAttnRows a;
+            a.Q = qkv; a.ldq = qd;
+            a.K = (const char*)kv->k + (size_t)l * kv->max_len * kvd * es; a.V = (const char*)kv->v + (size_t)l * kv->max_len * kvd * es;
+            a.ldk = a.ldv = kvd; a.prefix_len = kv->prefix_len;
+            a.tail_k = tk; a.tail_v = tv; a.tail_ld = kvd; a.tail_row = (long)tail_row; a.tail_len = tl + 1;
+            a.O = att; a.rows = R; a.hq = w.heads; a.hkv = w.kv_heads; a.head_dim = hd;
+            a.nsplit = nsplit; a.ws = split; a.ws_bytes = split_bytes;
+            { PROF(COGS_PROF_ATTN); COGS_TRY(cogs_k_attention_rows(st, a)); }
+        }
+        {
+            CogsGemm g; g.dtype = dt;
+            g.A = att; g.lda = qd_q; g.W = L.o_w; g.ldw = qd_q; g.C = x; g.ldc = H;
+            g.residual = x; g.ldr = H; g.M = R; g.N = H; g.K = qd_q;
+            { PROF(COGS_PROF_GEMM); COGS_TRY(cogs_k_gemm_rows(st, g)); }
+        }
+        { PROF(COGS_PROF_NORM); COGS_TRY(cogs_k_rmsnorm(st, dt, x, ln, L.post_ln, R, H, w.rms_eps)); }
+        {
+            CogsGemm g; g.dtype = dt;
+            g.A = ln; g.lda = H; g.W = L.gu_w; g.ldw = H; g.C = act; g.ldc = w.inter;
+            g.M = R; g.N = 2 * w.inter; g.K = H; g.act = COGS_ACT_SWIGLU;
+            { PROF(COGS_PROF_GEMM); COGS_TRY(cogs_k_gemm_rows(st, g)); }
+        }
+        {
+            CogsGemm g; g.dtype = dt;
+            g.A = act; g.lda = w.inter; g.W = L.down_w; g.ldw = w.inter; g.C = x; g.ldc = H;
+            g.residual = x; g.ldr = H; g.M = R; g.N = H; g.K = w.inter;
+            { PROF(COGS_PROF_GEMM); COGS_TRY(cogs_k_gemm_rows(st, g)); }
+        }
+    }
+    { PROF(COGS_PROF_NORM); COGS_TRY(cogs_k_rmsnorm(st, dt, x, ln, w.final_norm, R, H, w.rms_eps)); }
+    {
+        CogsGemm g; g.dtype = dt;
+        g.A = ln; g.lda = H; g.W = w.lm_head; g.ldw = H; g.C = logits; g.ldc = w.vocab;
+        g.M = R; g.N = w.vocab; g.K = H; g.out_f32 = 1;
+        { PROF(COGS_PROF_GEMM); COGS_TRY(cogs_k_gemm_rows(st, g)); }
+    }
+    kv->tail_len = tl + 1;
+    return COGS_OK;
 }
 
 }  // extern "C"

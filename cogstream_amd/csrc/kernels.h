@@ -85,6 +85,23 @@ struct CogsAttn {
 int cogs_k_attention_vit(hipStream_t st, const struct CogsAttn& a);   // attn_vit.hip: block-diagonal, hd 72, pre-scaled Q
 int cogs_k_attention_decode(hipStream_t st, const struct CogsAttn& a, float* part_o, float* part_ml);   // attn_decode.hip: one query row, hd 128, key-split partials
 int cogs_k_attention(hipStream_t st, const CogsAttn& a);
+// lockstep decode of `rows` sequences over one prompt (include/cogs.h cogs_attn_rows_desc): bf16, hd 128, pre-scaled Q
+struct CogsAttnRows {
+    const void* Q = nullptr; long ldq = 0;                       // [rows][hq * 128]
+    const void* K = nullptr; const void* V = nullptr; long ldk = 0, ldv = 0; int prefix_len = 0;   // shared keys
+    const void* tail_k = nullptr; const void* tail_v = nullptr;  // [rows][..][hkv * 128]: row r's own keys [0, tail_len)
+    long tail_ld = 0, tail_row = 0; int tail_len = 0;            //   key stride, stride between rows (elements)
+    void* O = nullptr;                                           // dense [rows][hq * 128]
+    int rows = 0, hq = 1, hkv = 1, head_dim = 0;
+    int nsplit = 1;                                              // splits of the shared keys (<= 127)
+    void* ws = nullptr; size_t ws_bytes = 0;                     // (nsplit + 1) * rows * hq * (head_dim + 2) floats
+};
+int cogs_k_attention_decode_rows(hipStream_t st, const CogsAttnRows& a, float* part_o, float* part_ml);   // attn_decode.hip: partials
+int cogs_k_attention_combine(hipStream_t st, const float* part_o, const float* part_ml, int nparts, int heads, int head_dim,
+                             void* O);   // attn.hip: nparts <= 128 partials of `heads` (row, head) slots -> dense bf16 O [heads][head_dim]
+int cogs_k_attention_rows(hipStream_t st, const CogsAttnRows& a);     // both of the above
+// gemm_rows.hip: bf16, 1 <= M <= 16, weights streamed once as the MFMA operand (not reachable through cogs_k_gemm: its plan is pinned)
+int cogs_k_gemm_rows(hipStream_t st, const CogsGemm& g);
 long cogs_k_gemm_launch_count();   // kernels launched by cogs_k_gemm so far in this process
 
 

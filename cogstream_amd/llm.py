@@ -14,6 +14,50 @@ from .runtime import get_handle
 from .weights import LlmConfig, PackedLlm
 
 
+MAX_RETURN_SEQUENCES = 16      # rows of one lockstep decode step: the 16 activation columns of the MFMA tile
+
+
+def check_num_return_sequences(n: int, do_sample: bool) -> int:
+    """the argument rules of generate(num_return_sequences=): transformers 4.46.3 refuses several greedy copies, the
+    lockstep step has 16 columns"""
+    n = int(n)
+    if n < 1 or n > MAX_RETURN_SEQUENCES:
+        raise ValueError(f"num_return_sequences has to be between 1 and {MAX_RETURN_SEQUENCES}, but is {n}")
+    if n > 1 and not do_sample:
+        raise ValueError(f"Greedy methods without beam search do not support `num_return_sequences` different than 1 (got {n}).")
+    return n
+
+
+def philox_offset(step: int, n_rows: int, row: int) -> int:
+    """sampler="device": the Philox offset of row `row` at step `step` of an n_rows-wide generate (= step at n_rows 1)"""
+    return step * n_rows + row
+
+
+def host_draw_block(generator, n_rows: int, vocab: int) -> torch.Tensor:
+    """sampler="host": the ONE [n_rows, vocab] Exponential(1) block torch.multinomial(probs[n_rows, vocab], 1) draws on the CPU
+    generator per step, row-major (row r of the block decides row r's token)"""
+    return torch.empty(n_rows, vocab, dtype=torch.float32).exponential_(1, generator=generator)
+
+
+def truncate_at_eos(rows: Sequence[Sequence[int]], eos) -> List[List[int]]:
+    """every row up to and including its first EOS"""
+    eos = set(int(e) for e in eos)
+    out = []
+    for r in rows:
+        hit = next((i for i, t in enumerate(r) if t in eos), None)
+        out.append(list(r) if hit is None else list(r[:hit + 1]))
+    return out
+
+
+def pad_rows(rows: Sequence[Sequence[int]], pad_token_id: int) -> torch.Tensor:
+    """ragged token rows -> int64 [N, L] right-padded with pad_token_id (what GenerationMixin returns for finished rows)"""
+    width = max((len(r) for r in rows), default=0)
+    out = torch.full((len(rows), width), int(pad_token_id), dtype=torch.int64)
+    for i, r in enumerate(rows):
+        out[i, :len(r)] = torch.tensor(list(r), dtype=torch.int64)
+    return out
+
+
 class KVCache:
     def __init__(self, cfg: LlmConfig, max_len: int, dtype, device):
         kvd = cfg.num_key_value_heads * cfg.head_dim
@@ -199,7 +243,8 @@ class Qwen2Engine:
                  sampler: str = "device", seed: Optional[int] = None,
                  cache: Optional[KVCache] = None, ignore_eos: bool = False,
                  prefix: Optional[PrefixKV] = None, prefilled: Optional[dict] = None,
-                 stage_times: Optional[dict] = None) -> List[int]:
+                 stage_times: Optional[dict] = None, num_return_sequences: int = 1,
+                 pad_token_id: Optional[int] = None):
         """GenerationMixin.generate with inputs_embeds: prefill, then one cogs_llm_forward per token.
         Returns the NEW token ids only. Logits processors run in HF order:
         repetition penalty -> custom (allowed-id mask) -> temperature -> top-k -> top-p.
@@ -209,7 +254,15 @@ class Qwen2Engine:
         Sampling (do_sample): cogs_sample on the device, tokens never visit the host. sampler="device": Philox draws
         keyed by `seed` (default: one draw of the CPU generator) and the step; sampler="host": the CPU generator
         (`generator`, default the global one) makes the [vocab] exponential draws of every step exactly as
-        torch.multinomial does in the reference's CPU run, so the sampled ids are the reference's."""
+        torch.multinomial does in the reference's CPU run, so the sampled ids are the reference's.
+        num_return_sequences = N > 1 (sampling only, N <= 16): N continuations of the one prefilled prompt, advanced in
+        lockstep by cogs_llm_decode_rows -> a list of N token lists (see _generate_rows); pad_token_id is accepted for
+        signature parity with GenerationMixin (the lists are ragged; CogReasoner.generate pads)."""
+        if check_num_return_sequences(num_return_sequences, do_sample) > 1:
+            return self._generate_rows(embeds, int(num_return_sequences), max_new_tokens=max_new_tokens, eos_token_id=eos_token_id,
+                                       temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
+                                       allowed_ids=allowed_ids, prompt_ids=prompt_ids, generator=generator, sampler=sampler,
+                                       seed=seed, cache=cache, ignore_eos=ignore_eos, prefix=prefix, prefilled=prefilled)
         S = embeds.shape[0]
         if stage_times is not None:        # bench.py's pipeline split: the prompt pass and the token loop, drained on both sides
             import time
@@ -285,6 +338,149 @@ class Qwen2Engine:
             # forwards issued past the EOS only wrote KV rows that are dropped again here
             cache.reset(min(cache.len, pos_start + stop_at - 1))
         return out
+
+    def decode_rows(self, embeds: torch.Tensor, kv: "L.KVRows") -> torch.Tensor:
+        """cogs_llm_decode_rows: one token per sequence, embeddings [R, H] -> fp32 logits [R, vocab]; advances kv.tail_len"""
+        self._activate()
+        embeds = embeds.contiguous()
+        R = embeds.shape[0]
+        nbytes = C.c_size_t()
+        L.check(L.lib.cogs_llm_decode_rows_workspace_bytes(self.handle.h, R, kv.prefix_len, C.byref(nbytes)),
+                "cogs_llm_decode_rows_workspace_bytes")
+        ws = self.handle.workspace("llm_rows", nbytes.value)
+        logits = torch.empty(R, self.cfg.vocab_size, device=self.device, dtype=torch.float32)
+        L.check(L.lib.cogs_llm_decode_rows(self.handle.h, L.current_stream(), embeds.data_ptr(), R, C.byref(kv), logits.data_ptr(),
+                                           ws.data_ptr(), ws.numel()), "cogs_llm_decode_rows")
+        return logits
+
+    def new_rows_kv(self, cache: KVCache, n_rows: int, tail_max: int):
+        """the cogs_kv_rows view of `cache` (its first cache.len rows are the shared prompt) + fresh tails for n_rows
+        sequences; the tail tensors are returned too (they own the memory)"""
+        kvd = self.cfg.num_key_value_heads * self.cfg.head_dim
+        tk = torch.empty(self.cfg.num_hidden_layers, n_rows, tail_max, kvd, device=self.device, dtype=self.dtype)
+        tv = torch.empty_like(tk)
+        kv = L.KVRows(cache.k.data_ptr(), cache.v.data_ptr(), cache.k.shape[1], cache.len, tk.data_ptr(), tv.data_ptr(), tail_max, 0)
+        return kv, tk, tv
+
+    def _generate_rows(self, embeds, N, *, max_new_tokens, eos_token_id, temperature, top_k, top_p, repetition_penalty,
+                       allowed_ids, prompt_ids, generator, sampler, seed, cache, ignore_eos, prefix, prefilled) -> List[List[int]]:
+        """GenerationMixin._sample on the N times expanded prompt, without expanding it: the prompt is prefilled once, the
+        first token of every row is drawn from the one processed prefill logits row, and the rows then advance in lockstep
+        (one multi-row step per token: every weight byte once per step) with their own repetition-penalty histories.
+        Row r of step s draws with Philox offset s * N + r (device sampler) or from row r of the step's [N, vocab] block of
+        the CPU generator (host sampler: what torch.multinomial on [N, vocab] consumes). A row that has produced an EOS is
+        cut there; it keeps being stepped until every row is done (rows do not influence one another). The shared cache is
+        left at the prompt length, so a PrefixKV stays valid. fp32 engines / head_dim != 128 have no multi-row kernels:
+        the same draws are made with single-row steps, one cache replayed per row and step."""
+        S = embeds.shape[0]
+        if prefilled is not None:
+            assert cache is not None and prefix is None and cache.len >= S and "logits" in prefilled
+            res = prefilled
+        elif prefix is not None:
+            assert cache is None
+            embeds = embeds.contiguous()
+            p = prefix.plan(embeds, S + max_new_tokens)
+            cache = prefix.cache
+            cache.reset(p)
+            prefix.rows = None
+            res = self.forward(embeds[p:], cache)
+            prefix.rows = embeds
+        else:
+            if cache is None:
+                cache = self.new_cache(S + max_new_tokens)
+            res = self.forward(embeds, cache)
+        P = cache.len                                   # the shared prompt: rows 0 .. P-1 of the cache
+        V = self.cfg.vocab_size
+        allowed = (torch.tensor(list(allowed_ids), dtype=torch.int32, device=self.device) if allowed_ids is not None else None)
+        eos = set() if ignore_eos else set(int(e) for e in eos_token_id)
+        n_prompt = int(prompt_ids.numel()) if prompt_ids is not None else 0
+        seen = torch.empty(N, n_prompt + max_new_tokens, dtype=torch.int64, device=self.device)
+        if n_prompt:
+            seen[:, :n_prompt] = prompt_ids.reshape(1, -1).to(self.device)
+        toks = seen[:, n_prompt:]
+        host = sampler == "host"
+        if not host and seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,), generator=generator).item())
+        need_proc = repetition_penalty != 1.0 or allowed is not None
+        top_p = 1.0 if top_p is None else top_p
+
+        def process(row_logits, r, n_seen):
+            if need_proc:
+                prev = seen[r, :n_seen] if (n_seen and repetition_penalty != 1.0) else None
+                ops.logits_process(row_logits, prev, repetition_penalty, allowed, 1.0)
+
+        def draw(row_logits, r, step, block):
+            ops.sample(row_logits, top_k or 0, top_p, draws=block[r] if host else None, seed=seed or 0,
+                       offset=philox_offset(step, N, r), temperature=temperature, out=toks[r, step:step + 1])
+
+        def done_rows(produced):
+            rows = toks[:, :produced].tolist()
+            return rows, all(any(t in eos for t in r) for r in rows) if eos else False
+
+        first = res["logits"]
+        process(first, 0, n_prompt)                     # every row has the same history so far: processed once
+        if max_new_tokens <= 0:
+            return [[] for _ in range(N)]
+
+        if self.dtype != torch.bfloat16 or self.cfg.head_dim != 128:
+            # sequential fallback, step-outer like the lockstep loop, so a step's [N, vocab] block of host draws is made, used
+            # and dropped within the step. The one cache is replayed per row: row r's private K/V rows (kept aside in
+            # tk / tv, [N][layers][max_new_tokens][kv_dim]) are copied behind the prompt, the single-row step appends one
+            # more, and that one is copied back. A row that has produced an EOS is no longer stepped.
+            tk = torch.empty((N, cache.k.shape[0], max_new_tokens, cache.k.shape[2]), device=self.device, dtype=self.dtype)
+            tv = torch.empty_like(tk)
+            live = list(range(N))
+            produced = 0
+            for step in range(max_new_tokens):
+                block = host_draw_block(generator, N, V).to(self.device, non_blocking=True) if host else None
+                for r in live:
+                    if step == 0:
+                        logits = first.clone()
+                    else:
+                        t = step - 1                     # private rows 0 .. t-1 are in tk[r]; this step appends row t
+                        cache.k[:, P:P + t] = tk[r, :, :t]
+                        cache.v[:, P:P + t] = tv[r, :, :t]
+                        cache.reset(P + t)
+                        logits = self.forward(self.embed_tokens(toks[r, step - 1:step]), cache)["logits"]
+                        tk[r, :, t] = cache.k[:, P + t]
+                        tv[r, :, t] = cache.v[:, P + t]
+                        process(logits, r, n_prompt + step)
+                    draw(logits, r, step, block)
+                produced = step + 1
+                if eos and (host or produced % 8 == 0) and produced < max_new_tokens:
+                    got = toks[:, :produced].tolist()
+                    live = [r for r in live if not any(t in eos for t in got[r])]
+                    if not live:
+                        break
+            cache.reset(P)
+            return truncate_at_eos(toks[:, :produced].tolist(), eos)
+
+        kv, tail_k, tail_v = self.new_rows_kv(cache, N, max_new_tokens)
+        check_every = 1 if host else 8
+        produced = 0
+        rows = None
+        for step in range(max_new_tokens):
+            block = host_draw_block(generator, N, V).to(self.device, non_blocking=True) if host else None
+            if step == 0:
+                for r in range(N):
+                    draw(first.clone(), r, 0, block)
+            else:
+                logits = self.decode_rows(self.embed_tokens(toks[:, step - 1].contiguous()), kv)
+                for r in range(N):
+                    process(logits[r], r, n_prompt + step)
+                    draw(logits[r], r, step, block)
+            produced = step + 1
+            last = produced == max_new_tokens
+            if eos and (produced % check_every == 0 or last):
+                rows, done = done_rows(produced)
+                if done:
+                    break
+                rows = None
+        if rows is None:
+            rows = toks[:, :produced].tolist()
+        del tail_k, tail_v
+        cache.reset(P)
+        return truncate_at_eos(rows, eos)
 
     def _draws(self, generator) -> torch.Tensor:
         """parity mode: the [vocab] Exponential(1) draws torch.multinomial(probs, 1) makes on the CPU generator

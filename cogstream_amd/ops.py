@@ -75,6 +75,59 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, 
     return out
 
 
+def gemm_rows(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, *, act: int = L.ACT_NONE,
+              residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, out_f32: bool = False,
+              rope_cos: Optional[torch.Tensor] = None, rope_sin: Optional[torch.Tensor] = None, rope_cols: int = 0,
+              head_dim: int = 0, q_scale: float = 0.0, q_cols: int = 0, row_stats: Optional[torch.Tensor] = None,
+              ln_ab: Optional[torch.Tensor] = None, col_c: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[M,N] = epilogue(a[M,K] @ w[N,K]^T) for 1 <= M <= 16 bf16 rows (cogs_gemm_rows in include/cogs.h): the weights are
+    streamed once whatever M is. row_stats / ln_ab / col_c exist to be refused (COGS_E_UNSUPPORTED)."""
+    _need_cuda(a, w, bias, residual, out, rope_cos, rope_sin, row_stats, ln_ab, col_c)
+    M, K = a.shape
+    N = w.shape[0]
+    assert w.shape[1] == K and a.stride(1) == 1 and w.stride(1) == 1
+    if out is None:
+        out = torch.empty(M, N // 2 if act == L.ACT_SWIGLU else N, device=a.device, dtype=torch.float32 if out_f32 else a.dtype)
+    d = L.GemmDesc()
+    d.dtype = dtype_code(a.dtype)
+    d.A, d.lda = ptr(a), a.stride(0)
+    d.W, d.ldw = ptr(w), w.stride(0)
+    d.C, d.ldc = ptr(out), out.stride(0)
+    d.bias = ptr(bias)
+    d.residual, d.ldr = ptr(residual), (residual.stride(0) if residual is not None else 0)
+    d.M, d.N, d.K = M, N, K
+    d.act, d.out_f32 = act, int(out_f32)
+    d.rope_cos, d.rope_sin, d.rope_cols, d.head_dim = ptr(rope_cos), ptr(rope_sin), rope_cols, head_dim
+    d.row_stats, d.ln_ab, d.col_c = ptr(row_stats), ptr(ln_ab), ptr(col_c)
+    check(L.lib.cogs_gemm_rows(current_stream(), C.byref(d), q_scale, q_cols), "cogs_gemm_rows")
+    return out
+
+
+def attention_rows(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, tail_k: torch.Tensor, tail_v: torch.Tensor, *,
+                   prefix_len: int, tail_len: int, hq: int, hkv: int, head_dim: int = 128, nsplit: int = 1,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """cogs_attention_rows: q [rows, hq*hd] (pre-scaled; may be a column view), shared k / v [>= prefix_len, hkv*hd], tails
+    [rows, tail_max, hkv*hd] -> dense [rows, hq*hd]"""
+    _need_cuda(q, k, v, tail_k, tail_v, out)
+    rows = q.shape[0]
+    assert tail_k.shape[0] == rows and tail_k.shape == tail_v.shape and tail_k.stride() == tail_v.stride()
+    assert all(t.stride(-1) == 1 for t in (q, k, v, tail_k, tail_v)) and k.shape[0] >= prefix_len and tail_k.shape[1] >= tail_len
+    if out is None:
+        out = torch.empty(rows, hq * head_dim, device=q.device, dtype=q.dtype)
+    assert out.is_contiguous()
+    ws = torch.empty((nsplit + 1) * rows * hq * (head_dim + 2), device=q.device, dtype=torch.float32)
+    d = L.AttnRowsDesc()
+    d.dtype = dtype_code(q.dtype)
+    d.Q, d.ldq = ptr(q), q.stride(0)
+    d.K, d.V, d.ldk, d.ldv, d.prefix_len = ptr(k), ptr(v), k.stride(0), v.stride(0), prefix_len
+    d.tail_k, d.tail_v, d.tail_ld, d.tail_row_stride, d.tail_len = ptr(tail_k), ptr(tail_v), tail_k.stride(1), tail_k.stride(0), tail_len
+    d.O = ptr(out)
+    d.rows, d.hq, d.hkv, d.head_dim = rows, hq, hkv, head_dim
+    d.nsplit, d.ws, d.ws_bytes = nsplit, ptr(ws), ws.numel() * 4
+    check(L.lib.cogs_attention_rows(current_stream(), C.byref(d)), "cogs_attention_rows")
+    return out
+
+
 def gemv_fp8(x: torch.Tensor, codes: torch.Tensor, scale: torch.Tensor, bias: Optional[torch.Tensor] = None, *,
              act: int = L.ACT_NONE, residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
              out_f32: bool = False, rope_cos: Optional[torch.Tensor] = None, rope_sin: Optional[torch.Tensor] = None,

@@ -91,7 +91,9 @@ const char* cogs_debug_list(void);
  * fields are appended at the end with 0 = "off" (round 5: cogs_gemm_desc.hm_rows / hm_cols, cogs_attn_desc.head_stride), and a
  * field left holding stack garbage switches a feature on. cogs_version() names the ABI revision: "0.2" added those three,
  * "0.3" cogs_lm_score / cogs_row_lse, "0.4" cogs_gemv_fp8 / cogs_quantize_fp8_rows / cogs_llm_attach_fp8 (new entry points
- * only; every older signature and structure is unchanged). */
+ * only; every older signature and structure is unchanged). Added since without a new revision string (new entry points
+ * and structures only): cogs_gemm_rows, cogs_attention_rows / cogs_attn_rows_desc, cogs_llm_decode_rows /
+ * cogs_llm_decode_rows_workspace_bytes / cogs_kv_rows. */
 
 /* C[M,N] = epilogue(A[M,K] . W[N,K]^T). nn.Linear / Conv2d(k=s=14) replacement
  * (model/modeling_videollama3_encoder.py:194-210,246-248,275,369-373; cogreasoner_chat.py:179-211).
@@ -164,6 +166,18 @@ cogs_status cogs_gemm(cogs_stream stream, const cogs_gemm_desc* d);
 /* (rstd, -rstd * mean) per row from the row_stats partials of a GEMM whose N is the LayerNorm width H */
 cogs_status cogs_ln_finalize(cogs_stream stream, const float* row_stats, int rows, int H, float eps, float* ln_ab);
 
+/* C[M,N] = epilogue(A[M,K] . W[N,K]^T) for 1 <= M <= 16 rows in bf16: the GEMM of a lockstep decode step over several
+ * sequences (cogs_llm_decode_rows). W is streamed exactly once, as the operand of v_mfma_f32_16x16x32_bf16 whose 16 columns
+ * are the M rows (fp32 sums); a small N splits K over the waves of a workgroup and adds the parts in a fixed order -- no
+ * floating-point atomics, the same call gives the same bits, and for a fixed M output row m holds the same bits whatever
+ * the other rows hold and whichever slot it sits in. Takes cogs_gemm's descriptor and its shape rules: K % 64 == 0, N % 4 == 0,
+ * lda / ldw multiples of 8 and >= K, A and W 16-byte aligned, ldc / ldr and the C / residual pointers multiples of 4 elements
+ * (else COGS_E_INVALID). Epilogues: bias, rotary with per-row tables (interleaved when rope_sin == NULL), q_scale (0 or 1 = off)
+ * on columns < q_cols (rotary epilogues only, as in cogs_gemv_fp8_desc), COGS_ACT_SWIGLU, residual (may alias C), out_f32.
+ * COGS_E_UNSUPPORTED, before any launch: dtype != COGS_DT_BF16, M > 16, ln_ab, row_stats, hm_rows, rope_lut, the GELUs.
+ * cogs_gemm does not dispatch here: its results for 2 <= M <= 16 stay what they were. */
+cogs_status cogs_gemm_rows(cogs_stream stream, const cogs_gemm_desc* d, float q_scale, int q_cols);
+
 /* W8A16 GEMV (single-token decode): C[N] = epilogue(scale[n] * sum_k x[k] * e4m3(W[n][k])). W holds OCP e4m3fn codes (one
  * byte per weight; 0x7F / 0xFF, the NaN codes, must not occur), scale one fp32 POWER OF TWO per output row -- what
  * cogs_quantize_fp8_rows writes -- so that a dequantised weight code * scale is exactly a bf16 value and the GEMV computes
@@ -234,6 +248,25 @@ typedef struct {
                              * Q, hq == hkv, no mask modes); anything else returns COGS_E_UNSUPPORTED. O stays token-major. */
 } cogs_attn_desc;
 cogs_status cogs_attention(cogs_stream stream, const cogs_attn_desc* d);
+
+/* Decode attention of `rows` (<= 16) sequences that share a prompt: query row r (hq heads, head_dim 128, bf16, already
+ * multiplied by softmax_scale * log2(e)) sees keys [0, prefix_len) of the shared K / V (token-major, head h at column
+ * h * 128, row strides ldk / ldv) and keys [0, tail_len) of its own tail at tail_k / tail_v + r * tail_row_stride (key
+ * stride tail_ld; all strides in elements, multiples of 8). prefix_len >= 1, tail_len >= 1. Per kv head the rows * (hq / hkv)
+ * query columns are packed into MFMA tiles of 16; the shared keys are split over nsplit (1 .. 127) workgroups per tile, every
+ * row's tail is one more partial, and one combine kernel merges the nsplit + 1 partials. O: dense [rows][hq * 128].
+ * ws >= (nsplit + 1) * rows * hq * (head_dim + 2) * 4 bytes. COGS_E_UNSUPPORTED: dtype != COGS_DT_BF16, head_dim != 128,
+ * hq / hkv > 16 or not integral, rows > 16. Zero-initialise the descriptor. */
+typedef struct {
+    int dtype;
+    const void* Q; int64_t ldq;
+    const void* K; const void* V; int64_t ldk, ldv; int prefix_len;
+    const void* tail_k; const void* tail_v; int64_t tail_ld, tail_row_stride; int tail_len;
+    void* O;
+    int rows, hq, hkv, head_dim;
+    int nsplit; void* ws; size_t ws_bytes;
+} cogs_attn_rows_desc;
+cogs_status cogs_attention_rows(cogs_stream stream, const cogs_attn_rows_desc* d);
 
 /* nn.LayerNorm (modeling_videollama3_encoder.py:382-384,475) / Qwen2RMSNorm; H % 8 == 0 */
 cogs_status cogs_layernorm(cogs_stream stream, int dtype, const void* x, void* y, const void* gamma,
@@ -498,6 +531,27 @@ cogs_status cogs_llm_workspace_bytes(cogs_handle h, int max_tokens, int max_cont
 cogs_status cogs_llm_forward(cogs_handle h, cogs_stream stream, const void* embeds, int S, cogs_kv* kv,
                              float* last_logits, float* pooled_mean, void* hidden_out, void* ws,
                              size_t ws_bytes);
+
+/* Lockstep decode of R (<= 16) continuations of ONE prompt: GenerationMixin.generate(num_return_sequences=R) behind
+ * model/cogreasoner_chat.py:802-807 expands the prompt R times; here the prompt's KV rows [0, prefix_len) of k / v (the cogs_kv
+ * layout) are shared and read once per step, and every sequence keeps only the rows it generated: tail_k / tail_v
+ * [layers][R][tail_max][kv_heads * head_dim]. All rows stand at position prefix_len + tail_len. */
+typedef struct {
+    void* k; void* v; int max_len;   /* shared cache, as cogs_kv */
+    int prefix_len;                  /* prompt rows every sequence sees */
+    void* tail_k; void* tail_v;
+    int tail_max;
+    int tail_len;                    /* rows every sequence has generated; advanced by cogs_llm_decode_rows */
+} cogs_kv_rows;
+cogs_status cogs_llm_decode_rows_workspace_bytes(cogs_handle h, int R, int max_prefix, size_t* bytes);
+/* One Qwen2 step over R new tokens, one per sequence, given as embeddings [R, hidden]: per layer RMSNorm, qkv
+ * (cogs_gemm_rows; bias, rotary at the common position, pre-scaled Q), the new K / V rows into the tails, cogs_attention_rows,
+ * o + residual, RMSNorm, gate / up SwiGLU, down + residual; then the final norm and the lm_head -> logits fp32 [R, vocab].
+ * Every weight byte is read once per step. bf16 and head_dim 128 only (else COGS_E_UNSUPPORTED); hidden, inter and
+ * heads * head_dim must be multiples of 64. With e4m3 codes attached the step reads the dequantised matrices of
+ * cogs_llm_weights; cogs_debug_get("llm_last_decode_fp8") then reports 0. Row r's logits do not depend on the other rows. */
+cogs_status cogs_llm_decode_rows(cogs_handle h, cogs_stream stream, const void* embeds, int R, cogs_kv_rows* kv,
+                                 float* logits, void* ws, size_t ws_bytes);
 
 /* Teacher-forced scoring: the outputs of cogs_row_lse for logits = lm_head(hidden) WITHOUT the [S, vocab] logits --
  * Qwen2ForCausalLM.forward(labels=) / ForCausalLMLoss behind forward_train and forward (model/cogreasoner_chat.py:604-693,
