@@ -47,7 +47,7 @@
     X(attn_prio, 2, "prompt attention wave priorities: 0 none, 1 MFMA phases raised, 2 softmax phase raised")               \
     X(attn_light_first, 0, "1: causal query tiles issued lightest first")                                                   \
     X(attn_nq, 0, "general kernel: 1 / 2 forces 16 / 32 query rows per wave")                                              \
-    /* ---- encoder / LLM drivers (csrc/capi.hip), k-means ---- */                                                          \
+    /* ---- encoder / LLM drivers (csrc/capi_vit.hip, capi_llm.hip), k-means */                                            \
     X(vit_split_max, 1099511627776LL, "clips above this many patches are encoded on one stream")                           \
     X(llm_split_keys, 0, "> 0: keys per split of the decode attention (0: chosen from the context)")                        \
     X(llm_decode_fp8, 1, "cogs_llm_forward with e4m3 weights attached (cogs_llm_attach_fp8): 1 single-token steps read them, 0 the dequantised bf16 / fp32 copy (the in-process A/B)") \

@@ -1,4 +1,4 @@
-// Internal launcher interface between the C-ABI layer (capi.hip) and the kernel files.
+// Internal launcher interface between the C-ABI layer (capi.hip, capi_vit.hip, capi_llm.hip) and the kernel files.
 // Every launcher enqueues on the given stream, never synchronises, never allocates, and
 // returns a COGS_* status (0 = ok).
 #pragma once

@@ -1,5 +1,5 @@
 // Teacher-forced scoring: per-row log-sum-exp / target logit / first-maximum argmax of a logits matrix that is never
-// materialised as a whole. The caller (capi.hip: cogs_lm_score, cogs_row_lse) walks row blocks x vocabulary panels; a
+// materialised as a whole. The caller (capi_llm.hip: cogs_lm_score, capi.hip: cogs_row_lse) walks row blocks x vocabulary panels; a
 // panel [rows_b, width] of fp32 logits is folded into per-row running state (max, sum of exp relative to the max,
 // argmax) by the online-softmax update, and a last kernel turns the state into lse = max + log(sum).
 //

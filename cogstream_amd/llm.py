@@ -236,6 +236,29 @@ class Qwen2Engine:
                                                 out.data_ptr(), ws.data_ptr(), ws.numel()), "cogs_llm_forward_segments")
         return out
 
+    def _prefill(self, embeds, max_new_tokens, cache, prefix, prefilled):
+        """the prompt pass of generate(): -> (forward result with the prompt's last-row logits, the cache that now holds the
+        prompt, position of the first generated token). `prefilled`: the caller has run it; `prefix`: only the rows that
+        differ from the previous call's are run; else the whole prompt, into `cache` or a new one"""
+        S = embeds.shape[0]
+        if prefilled is not None:
+            assert cache is not None and prefix is None and cache.len >= S and "logits" in prefilled
+            return prefilled, cache, cache.len
+        if prefix is not None:
+            assert cache is None
+            embeds = embeds.contiguous()
+            p = prefix.plan(embeds, S + max_new_tokens)
+            cache = prefix.cache
+            cache.reset(p)
+            prefix.rows = None          # not valid while this call is rewriting the cache
+            res = self.forward(embeds[p:], cache)
+            prefix.rows = embeds        # rows 0..S-1 are prefilled; decode rows behind them are never reused
+            return res, cache, S
+        if cache is None:
+            cache = self.new_cache(S + max_new_tokens)
+        pos_start = cache.len + S
+        return self.forward(embeds, cache), cache, pos_start
+
     def generate(self, embeds: torch.Tensor, *, max_new_tokens: int, eos_token_id: Sequence[int] = (),
                  do_sample: bool = False, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0,
                  repetition_penalty: float = 1.0, allowed_ids: Optional[Sequence[int]] = None,
@@ -263,30 +286,11 @@ class Qwen2Engine:
                                        temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
                                        allowed_ids=allowed_ids, prompt_ids=prompt_ids, generator=generator, sampler=sampler,
                                        seed=seed, cache=cache, ignore_eos=ignore_eos, prefix=prefix, prefilled=prefilled)
-        S = embeds.shape[0]
         if stage_times is not None:        # bench.py's pipeline split: the prompt pass and the token loop, drained on both sides
             import time
             torch.cuda.synchronize()
             t_start = time.perf_counter()
-        if prefilled is not None:
-            assert cache is not None and prefix is None and cache.len >= S and "logits" in prefilled
-            pos_start = cache.len
-            res = prefilled
-        elif prefix is not None:
-            assert cache is None
-            embeds = embeds.contiguous()
-            p = prefix.plan(embeds, S + max_new_tokens)
-            cache = prefix.cache
-            cache.reset(p)
-            prefix.rows = None          # not valid while this call is rewriting the cache
-            res = self.forward(embeds[p:], cache)
-            prefix.rows = embeds        # rows 0..S-1 are prefilled; decode rows behind them are never reused
-            pos_start = S
-        else:
-            if cache is None:
-                cache = self.new_cache(S + max_new_tokens)
-            pos_start = cache.len + S
-            res = self.forward(embeds, cache)
+        res, cache, pos_start = self._prefill(embeds, max_new_tokens, cache, prefix, prefilled)
         if stage_times is not None:
             torch.cuda.synchronize()
             t_loop = time.perf_counter()
@@ -372,23 +376,7 @@ class Qwen2Engine:
         cut there; it keeps being stepped until every row is done (rows do not influence one another). The shared cache is
         left at the prompt length, so a PrefixKV stays valid. fp32 engines / head_dim != 128 have no multi-row kernels:
         the same draws are made with single-row steps, one cache replayed per row and step."""
-        S = embeds.shape[0]
-        if prefilled is not None:
-            assert cache is not None and prefix is None and cache.len >= S and "logits" in prefilled
-            res = prefilled
-        elif prefix is not None:
-            assert cache is None
-            embeds = embeds.contiguous()
-            p = prefix.plan(embeds, S + max_new_tokens)
-            cache = prefix.cache
-            cache.reset(p)
-            prefix.rows = None
-            res = self.forward(embeds[p:], cache)
-            prefix.rows = embeds
-        else:
-            if cache is None:
-                cache = self.new_cache(S + max_new_tokens)
-            res = self.forward(embeds, cache)
+        res, cache, _ = self._prefill(embeds, max_new_tokens, cache, prefix, prefilled)
         P = cache.len                                   # the shared prompt: rows 0 .. P-1 of the cache
         V = self.cfg.vocab_size
         allowed = (torch.tensor(list(allowed_ids), dtype=torch.int32, device=self.device) if allowed_ids is not None else None)

@@ -698,3 +698,51 @@ def test_encode_project_equals_encoder_then_projector_bit_for_bit(dev):
             assert torch.equal(got, want), (s, float((got.float() - want.float()).abs().max()))
     finally:
         L.check(L.lib.cogs_vit_set_streams(enc.handle.h, 2))
+
+
+def test_workspace_sizes_are_the_sum_of_their_buffers(dev):
+    """The *_workspace_bytes queries return the one number callers cache their workspaces by: every buffer of the layout,
+    each rounded up to 256 bytes, in the tiny bf16 head_dim-128 Qwen2 (tests/test_gpu_rows.py) and the tiny ViT of
+    tests/golden/vit_tiny.npz. The split count is test_gpu_rows._nsplit without its cap of 127 (128 for the single-row
+    step: no tails there); no case here comes near either cap."""
+    import ctypes as C
+    from cogstream_amd import _lib as L
+
+    def total(*sizes):
+        return sum((int(s) + 255) // 256 * 256 for s in sizes)
+
+    def nsplit(ctx):
+        return max(min(max((ctx + 255) // 256, 32), (ctx + 63) // 64), 1)
+
+    def query(fn, *args):
+        n = C.c_size_t()
+        L.check(fn(*args, C.byref(n)))
+        return n.value
+
+    cfg, _, eng = _llm(dev, torch.bfloat16)
+    H, I, hq, hkv, hd = cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
+    assert hd == 128
+    qd = (hq + 2 * hkv) * hd
+    eng._activate()
+    for S, ctx in ((1, 1), (5, 5), (1, 300), (24, 24)):
+        want = total(S * H * 2, S * H * 2, S * qd * 2, S * hq * hd * 2, S * I * 2,      # x, ln, qkv, attention out, MLP hidden
+                     S * (hd // 2) * 2 * 4,                                             # (cos, sin) table
+                     nsplit(ctx) * hq * (hd + 2) * 4,                                   # decode-attention partials
+                     S * 4, (S + 1) * 4)                                                # row positions, cu_seqlens
+        assert query(L.lib.cogs_llm_workspace_bytes, eng.handle.h, S, ctx) == want, (S, ctx)
+    for R, prefix in ((1, 1), (3, 40), (16, 300)):
+        want = total(R * H * 2, R * H * 2, R * qd * 2, R * hq * hd * 2, R * I * 2, R * (hd // 2) * 2 * 4, R * 4,
+                     (nsplit(prefix) + 1) * R * hq * (hd + 2) * 4)                      # prefix partials + one for the tails
+        assert query(L.lib.cogs_llm_decode_rows_workspace_bytes, eng.handle.h, R, prefix) == want, (R, prefix)
+
+    vcfg, _, enc = _vit(dev, torch.bfloat16, 0)
+    VH, vhd = vcfg.hidden_size, vcfg.hidden_size // vcfg.num_attention_heads
+    ipad, ppad = enc.packed.inter_pad, enc.packed.patch_pad
+    assert (ipad, ppad) == (256, 640)                                                   # 200 and 588 up to the 64-wide K slab
+    enc._activate()
+    for N in (4, 64):
+        want = total(N * ppad * 2, N * VH * 2, N * VH * 2, N * max(4 * VH, ipad) * 2,   # padded patches, x, ln, [qkv | att] / MLP
+                     N * (vhd // 2) * 2 * 4,                                            # (cos, sin) table
+                     (N + 1) * 4, N * 4, N * 4,                                         # cu_seqlens (frames <= patches), lo, hi
+                     28 * 1024) + 256 * 1024                                            # rotary LUT; tables of further frame ranges
+        assert query(L.lib.cogs_vit_workspace_bytes, enc.handle.h, N) == want, N
