@@ -31,11 +31,6 @@ namespace {
 // the reference BEFORE its exponentials instead of scaling (O, l) behind them (exp2 of the difference would overflow towards
 // inf, and inf * 2^-dd = NaN); up to 2^64 a row sum of 64 keys fits fp32 and P is exact in bf16
 constexpr float PRE_FAR = 64.f;
-#ifdef COGS_NO_PRE_FAR          // A/B builds only (tools/build_alt.sh attn -DCOGS_NO_PRE_FAR): what the far test costs
-#define COGS_PRE_FAR_ON false
-#else
-#define COGS_PRE_FAR_ON true
-#endif
 
 struct AttnArgs {
     const void* Q; const void* K; const void* V; void* O;
@@ -338,7 +333,7 @@ __global__ __launch_bounds__(128 * (4 / NQ), NQ == 1 ? 4 : ((PRE && HD == 72) ? 
                     m_ref[qi] = d0;
                     d = 0.f;
                 }
-                if (COGS_PRE_FAR_ON && __any(d > PRE_FAR)) {
+                if (__any(d > PRE_FAR)) {
                     // far above the reference (rare, wave-uniform): exp2(score - OLD reference) would overflow towards inf, and the
                     // factor applied afterwards would turn that into inf * 0 = NaN. Move the reference of those rows NOW: (O, l) take
                     // 2^-dd, the scores are shifted, and the test behind the exponentials finds nothing left to do for them
@@ -679,16 +674,11 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_dma_kernel(AttnArgs p) {
                 for (int qi = 0; qi < NQ; ++qi) {
                     const float nm = -m_ref[qi];
                     const f32x4 c0 = f32x4{nm, nm, nm, nm};
-#ifdef PF_ABL_NOQK
-                    if (s == 0) sacc[ut][qi] = c0; else sacc[ut][qi][0] += __builtin_bit_cast(float, kf[0] & 0x3f000000u);
-#else
                     sacc[ut][qi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
                         __builtin_bit_cast(bf16x8, kf), qf[qi][s], s == 0 ? c0 : sacc[ut][qi], 0, 0, 0);
-#endif
                 }
             }
         }
-        #if !defined(PF_ABL_NOQK) && !defined(PF_ABL_NOPV)
         if constexpr (DEEP && !MASKED) {          // 16 reads, 32 MFMAs: 6 reads, then a read per pair of MFMAs
             __builtin_amdgcn_sched_group_barrier(0x100, 6, 0);
 #pragma unroll
@@ -698,7 +688,6 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_dma_kernel(AttnArgs p) {
             }
             __builtin_amdgcn_sched_group_barrier(0x008, 12, 0);
         }
-#endif
         { const int pm = PRIO >= 0 ? PRIO : p.prio_mode; if (pm == 1) __builtin_amdgcn_s_setprio(0); else if (pm == 2) __builtin_amdgcn_s_setprio(1); }
         bf16x8 pf[2][NQ];
         float post_alpha[NQ];
@@ -725,11 +714,7 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_dma_kernel(AttnArgs p) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) { sv[ut][r] = sacc[ut][qi][r]; d = fmaxf(d, sacc[ut][qi][r]); }
             }
-#ifdef PF_ABL_NOMAX
-            d = 0.f;
-#else
             if (!DEEP || first_tile) d = colgroup_max(d);       // DEEP: d stays this lane's own maximum (4 of the row's 16 keys per block)
-#endif
             if (first_tile) {
                 const float d0 = (d == -INFINITY) ? 0.f : d;
 #pragma unroll
@@ -748,7 +733,7 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_dma_kernel(AttnArgs p) {
             // Round-4 form (DEEP = 0, A/B only): the deferred factor behind the PV product stays; only a crossing of more than
             // 2^PRE_FAR takes this path.
             constexpr float MOVE_THR = DEEP ? PREFILL_THR : PRE_FAR;
-            if (COGS_PRE_FAR_ON && __any(d > MOVE_THR)) {
+            if (__any(d > MOVE_THR)) {
                 const float dr = DEEP ? colgroup_max(d) : d;
                 const float dd = dr > MOVE_THR ? dr : 0.f;
                 const float al = __builtin_amdgcn_exp2f(-dd);
@@ -767,11 +752,7 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_dma_kernel(AttnArgs p) {
             for (int ut = 0; ut < 4; ++ut)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-#ifdef PF_ABL_NOEXP
-                    const float pv = sv[ut][r];
-#else
                     const float pv = __builtin_amdgcn_exp2f(sv[ut][r]);
-#endif
                     sv[ut][r] = pv;
                     psum += pv;
                 }
@@ -808,14 +789,9 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_dma_kernel(AttnArgs p) {
                 const bf16x8 vf = __builtin_bit_cast(bf16x8, w);
 #pragma unroll
                 for (int qi = 0; qi < NQ; ++qi)
-#ifdef PF_ABL_NOPV
-                    oacc[d][qi][0] += __builtin_bit_cast(float, (__builtin_bit_cast(u32x4, vf)[0] ^ __builtin_bit_cast(u32x4, pf[u][qi])[0]) & 0x3f000000u);
-#else
                     oacc[d][qi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[u][qi], oacc[d][qi], 0, 0, 0);
-#endif
             }
         }
-        #if !defined(PF_ABL_NOQK) && !defined(PF_ABL_NOPV)
         if constexpr (DEEP && !MASKED) {          // 32 transposed reads, 32 MFMAs: 8 reads lead (beside the exponentials)
             __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);
 #pragma unroll
@@ -825,7 +801,6 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_dma_kernel(AttnArgs p) {
             }
             __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
         }
-#endif
         if constexpr (!DEEP) {        // the deferred factor exists in the round-4 form only
 #pragma unroll
         for (int qi = 0; qi < NQ; ++qi) {
@@ -863,14 +838,8 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_dma_kernel(AttnArgs p) {
     auto tile_tail = [&](int kt) {
         // tile kt + 1 (issued at the top of this iteration) has landed for this wave; after the barrier for every wave,
         // and nobody reads tile kt's buffer any more -- it is the one tile kt + 2 goes into
-#ifndef PF_ABL_NOSYNC
-#ifndef PF_ABL_NOWAIT
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-#ifndef PF_ABL_NOBAR
         __builtin_amdgcn_s_barrier();
-#endif
-#endif
     };
     int kt = 0;
     if (nt > 0) {                                   // tile 0, the copy that sets the reference
@@ -881,9 +850,7 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_dma_kernel(AttnArgs p) {
         kt = 1;
     }
     for (; kt < t_mid; ++kt) {
-#ifndef PF_ABL_NOSYNC
         if (kt + 1 < nt) issue_tile(kt + 1);
-#endif
         process_tile(kt, std::false_type{}, std::false_type{});
         tile_tail(kt);
     }

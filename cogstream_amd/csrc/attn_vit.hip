@@ -49,26 +49,6 @@ struct VitAttnArgs {
 
 constexpr float RESCALE_THR = 6.0f;
 
-#if defined(COGS_ATTN_STAMPS) || defined(COGS_PIPE_STAMPS) || defined(COGS_PHASE_STAMPS)   // diagnostic builds (tools/micro/attn_vit_micro.cpp)
-__device__ unsigned long long g_attn_stamps[8];
-__device__ unsigned long long g_tail_stamps[8];
-#endif
-#ifdef COGS_LIFE_STAMPS   // tools/micro/attn_vit_micro.cpp: summed workgroup lifetimes (s_memtime), wave 0
-__device__ unsigned long long g_av_life[8];
-#define LIFE_NOW(v) do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) :: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
-#define LIFE_ADD(i, v) do { if (threadIdx.x == 0) atomicAdd(&g_av_life[i], (unsigned long long)(v)); } while (0)
-#else
-#define LIFE_NOW(v) do {} while (0)
-#define LIFE_ADD(i, v) do {} while (0)
-#endif
-// the workgroup whose stamps are kept is named by its place in the dispatch order (the grid is 3-D since round 6)
-#define COGS_AV_LINEAR_ID ((int)((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x))
-#ifdef COGS_ATTN_STAMPS   // where does a tile's time go, wave 0 of one workgroup
-#define STAMP(acc_) do { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); acc_ += now_ - st_prev; st_prev = now_; } while (0)
-#else
-#define STAMP(acc_) do {} while (0)
-#endif
-
 __device__ __forceinline__ float bf16_round(float x) { return bf2f(f2bf(x)); }
 
 template <int HD>
@@ -183,9 +163,6 @@ __global__ __launch_bounds__(256, 2) void attn_vit_kernel(VitAttnArgs p) {
     float sh = 0.f;          // the row's reference (bf16-exact); -sh sits in Q's pad column
     bool first = true;
 
-#ifdef COGS_ATTN_STAMPS
-    unsigned long long st_bar = 0, st_stage = 0, st_qk = 0, st_sm = 0, st_pv = 0, st_prev = __builtin_amdgcn_s_memtime();
-#endif
     load_k(0); load_v(0);
     write_k(smem); write_v(smem);
     if (nt > 1) { load_k(1); load_v(1); }
@@ -232,7 +209,6 @@ __global__ __launch_bounds__(256, 2) void attn_vit_kernel(VitAttnArgs p) {
             }
         };
         qk();
-        STAMP(st_qk);
         // V^T fragments of d-block 0, issued before the softmax so that their LDS latency hides under it
         auto read_v = [&](int b, int kb, int s2) -> u32x4 {
             const char* va = buf + v_rd + (32 * kb + 16 * s2) * VRS + b * 64;
@@ -286,10 +262,6 @@ __global__ __launch_bounds__(256, 2) void attn_vit_kernel(VitAttnArgs p) {
                 for (int w = 0; w < 4; ++w)
                     pf[kb][s2][w] = pack_bf2(__builtin_amdgcn_exp2f(sc[kb][8 * s2 + 2 * w]),
                                              __builtin_amdgcn_exp2f(sc[kb][8 * s2 + 2 * w + 1]));
-#ifdef COGS_ATTN_STAMPS
-        asm volatile("" :: "v"(pf[1][1]));
-#endif
-        STAMP(st_sm);
         // O^T[d][q] += V^T[d][key] . P^T[key][q]
 #pragma unroll
         for (int b = 0; b < DB; ++b) {
@@ -310,28 +282,13 @@ __global__ __launch_bounds__(256, 2) void attn_vit_kernel(VitAttnArgs p) {
     // made hipcc merge the accumulators of the two paths with 24 register-pair copies per tile
     const int full_tiles = (qe - qs) >> 6;
     for (int t = 0; t < full_tiles; ++t) {
-        STAMP(st_pv);
         __syncthreads();                        // tile t is in buffer t&1; everyone is done with buffer (t+1)&1
-        STAMP(st_bar);
         if (t + 1 < nt) {
-#ifndef ABL_NOWRITE
             write_k(smem + ((t + 1) & 1) * BUF); write_v(smem + ((t + 1) & 1) * BUF);
-#endif
-#ifndef ABL_NOLOAD
             if (t + 2 < nt) { load_k(t + 2); load_v(t + 2); }
-#endif
         }
-        STAMP(st_stage);
-#ifndef ABL_NOCOMPUTE
         if (wave_active) compute(smem + (t & 1) * BUF, qs + t * 64, std::false_type{});   // else: only stage and synchronise
-#endif
     }
-#ifdef COGS_ATTN_STAMPS
-    if (COGS_AV_LINEAR_ID == 1234 && tid == 0) {
-        g_attn_stamps[0] = st_bar; g_attn_stamps[1] = st_stage; g_attn_stamps[2] = st_qk; g_attn_stamps[3] = st_sm;
-        g_attn_stamps[4] = st_pv; g_attn_stamps[5] = full_tiles;
-    }
-#endif
     if (full_tiles < nt) {
         __syncthreads();
         if (wave_active) compute(smem + (full_tiles & 1) * BUF, qs + full_tiles * 64, std::true_type{});
@@ -385,8 +342,8 @@ __global__ __launch_bounds__(256, 2) void attn_vit_kernel(VitAttnArgs p) {
 //       constant chunk [1, 0 x7] / zeros behind the tile instead.
 // Rows past the segment end are read from its last row (finite data, their scores are masked), never from outside.
 //
-// Stamped life of a workgroup (cfg2 shape, 15 tiles, -DCOGS_PIPE_STAMPS, shader cycles): 7 500 from kernel entry to "Q
-// and tile 0 landed" (kernel arguments, segment bounds, Q + first tiles: three dependent round trips on a loaded chip),
+// Stamped life of a workgroup (cfg2 shape, 15 tiles, shader cycles, profiles/r5_attn_vit_stamps.txt): 7 500 from kernel entry to
+// "Q and tile 0 landed" (kernel arguments, segment bounds, Q + first tiles: three dependent round trips on a loaded chip),
 // 900 to S(0), 29 000 in the tile loop (1 930 per tile at two workgroups per CU, i.e. 965 per wave and tile on a SIMD
 // against 704 cycles of MFMA and an issue-bound floor near 880), 1 900 for normalise + store. A fifth of its life is the
 // entry, during which its SIMDs hold one wave only. Keeping the K/V stream running across the seam was built three times
@@ -399,8 +356,8 @@ __global__ __launch_bounds__(256, 2) void attn_vit_kernel(VitAttnArgs p) {
 // K/V tile staged once for twice the rows, 2.25 instead of 4.5 LDS-DMA pieces per wave and tile, half as many workgroup
 // entries per (frame, head)). Bit-identical outputs; attention of a cfg2 step 9.84 -> 11.03 ms, cfg3 4.26 -> 4.78 ms
 // (in-process A/B, tools/encoder_ab.py): with one workgroup per CU nothing computes during a workgroup's entry and exit
-// (13-15 % of its life, stamps below), and the two waves of a SIMD, now in one workgroup, are put back in step by every
-// tile barrier. Two 4-wave workgroups per CU it stays.
+// (13-15 % of its life, profiles/r5_attn_vit_stamps.txt), and the two waves of a SIMD, now in one workgroup, are put back in step
+// by every tile barrier. Two 4-wave workgroups per CU it stays.
 // Round 6: R > 0 = the shape of the ragged end is compile-time. Every segment of the launch has the same length (p.uniform_len: one
 // video), nt >= 4 key tiles of which the last has NLB (1 or 2) 32-key blocks, and R = 4 + ((nt - 4) & 3) in 4..7 is the number of
 // tiles behind the four-tile main loop -- chosen so that nt - R is a multiple of 4 (the first of them sits in ring slot 0) and that
@@ -410,51 +367,26 @@ __global__ __launch_bounds__(256, 2) void attn_vit_kernel(VitAttnArgs p) {
 // arithmetic in the same order: bit-identical outputs (checksums of profiles/r6_attn_vit_ct_end_ab.txt, tests/test_gpu_ops.py).
 template <int HD, int R = 0, int NLB = 0>
 __global__ __launch_bounds__(256, 2) void attn_vit_pipe_kernel(VitAttnArgs p) {
-    constexpr int NT = 256, QB = 128, NS = 4, NW = 4;
+    constexpr int QB = 128, NS = 4, NW = 4;          // 256 threads
     static_assert(HD % 8 == 0 && HD % 16 == 8 && HD < 96, "pad column HD must open a fresh 16-byte chunk inside the last k-step");
     constexpr int KS = (HD + 8) / 16, DB = (HD + 8 + 31) / 32, CH = HD / 8;
     constexpr int RS = HD * 2;                        // LDS row stride = the row itself (144 B)
     constexpr int TILE = 64 * RS;                     // 9216
-    constexpr int PIECES = TILE / 1024;               // 9 DMA pieces of 1 KiB per matrix and tile
-    static_assert(TILE % 1024 == 0, "a tile is a whole number of 1 KiB pieces");
+    static_assert(TILE % 1024 == 0, "a tile is a whole number of 1 KiB pieces");      // 9 DMA pieces per matrix and tile
     constexpr int C_ONE = 2 * TILE, C_ZERO = 2 * TILE + 16, STAGE = 2 * TILE + 64;     // [K | V | one-chunk | zero-chunk | -]
-#ifdef ABL_ONE_WG      // ablation (tools/attn_abl.sh): one workgroup per CU -- the LDS request no longer fits twice
-    __shared__ __attribute__((aligned(16))) char smem[NS * STAGE + 16384];
-#else
     __shared__ __attribute__((aligned(16))) char smem[NS * STAGE];
-#endif
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int h = lane >> 5, r32 = lane & 31;
-#ifdef COGS_PIPE_STAMPS     // diagnostic build (tools/micro/attn_vit_micro.cpp): life of one workgroup (wave 0) in shader cycles
-    unsigned long long ps_t[10];
-    int ps_n = 0;
-#define PSTAMP() do { unsigned long long t_; __builtin_amdgcn_sched_barrier(0); asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); __builtin_amdgcn_sched_barrier(0); ps_t[ps_n++] = t_; } while (0)
-#else
-#define PSTAMP() do {} while (0)
-#endif
-#ifdef COGS_PHASE_STAMPS      // tools/experiments/attn_vit_phases.sh: where a main-loop tile's time goes, wave 0 of one workgroup
-#define PHT(v) do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) :: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define PHT(v) do {} while (0)
-#endif
-    PSTAMP();      // 0: kernel entry
-    unsigned long long life0 = 0, life1 = 0;
-    LIFE_NOW(life0);
     int seg, head, qb;                                           // XCD-aware 3-D grid, see attn_vit_kernel
     if (p.xcd_order) { qb = blockIdx.x >> 3; head = blockIdx.y * 8 + (blockIdx.x & 7); seg = blockIdx.z; }
     else { qb = blockIdx.x; head = blockIdx.y; seg = blockIdx.z; }
     const int qs = (R > 0 || p.uniform_len > 0) ? seg * p.uniform_len : p.cu[seg];
     const int qe = (R > 0 || p.uniform_len > 0) ? qs + p.uniform_len : p.cu[seg + 1];
     const int q0 = qs + qb * QB;
-#ifdef COGS_PIPE_STAMPS2
-    asm volatile("" :: "s"(qs), "s"(qe));
-    PSTAMP();      // segment bounds here
-#endif
     if (q0 >= qe) return;
     const int nt = (qe - qs + 63) >> 6;
-    const int full_tiles = (qe - qs) >> 6;
 
     if (tid < NS) {                                              // constant chunks, written once
         *reinterpret_cast<u32x4*>(smem + tid * STAGE + C_ONE) = u32x4{0x00003f80u, 0, 0, 0};
@@ -473,19 +405,14 @@ __global__ __launch_bounds__(256, 2) void attn_vit_pipe_kernel(VitAttnArgs p) {
     }
 
     // DMA pieces: piece j (0..8) of a matrix covers chunks 64j..64j+63 of the tile image (chunk c = row c / 9, 16-byte
-    // column c % 9). Wave w issues pieces w, w + NW, ... < 8 of K and of V (two each with 4 waves, one with 8); piece 8 of
-    // K goes to wave 0, of V to wave 1 (-DAV_WAVE_NINTH, the form up to round 5) -- round 6: the ninth pieces go out in HALVES, one
-    // half per wave (K lanes 0-31: wave 0, K lanes 32-63: wave 1, V: waves 2 and 3) under a half EXEC mask: every wave issues the
-    // same 2 NPI + 1 requests per tile, selected by scalar moves instead of two wave-dependent branches behind the tile's barrier,
-    // and the counted waits are exact for all four waves.
+    // column c % 9). Wave w issues pieces w, w + NW, ... < 8 of K and of V (two each with 4 waves, one with 8). The ninth pieces go
+    // out in HALVES, one half per wave (K lanes 0-31: wave 0, K lanes 32-63: wave 1, V: waves 2 and 3) under a half EXEC mask: every
+    // wave issues the same 2 NPI + 1 requests per tile, selected by scalar moves, and the counted waits are exact for all four waves.
+    // (Up to round 5 piece 8 of K went whole to wave 0 and of V to wave 1, behind two wave-dependent branches after the tile's
+    // barrier: 0.9 % slower, profiles/r6_attn_vit_ct_end_ab.txt.)
     constexpr int NPI = 8 / NW;                                  // regular pieces per matrix and wave
-#ifdef AV_WAVE_NINTH
-    const int n_own = 2 * NPI + (wid < 2 ? 1 : 0);               // this wave's DMA instructions per tile
-#else
-    const int n_own = 2 * NPI + 1;
     const unsigned long long ninth_exec = (wid & 1) ? 0xffffffff00000000ull : 0x00000000ffffffffull;
     const bool ninth_v = wid >= 2;
-#endif
     int pc_row[NPI + 1], pc_off[NPI + 1];                        // per-lane row and byte offset of the wave's pieces
 #pragma unroll
     for (int i = 0; i < NPI + 1; ++i) {
@@ -506,9 +433,6 @@ __global__ __launch_bounds__(256, 2) void attn_vit_pipe_kernel(VitAttnArgs p) {
     // (M0 is a reserved register for hipcc: it never keeps a value there across statements and sets it right in front
     // of its own uses, so writing it here needs no clobber -- naming it in the clobber list only draws a warning)
     auto dma16 = [&](const bf16_t* base, int off_bytes, unsigned lds) {
-#ifdef AV_ABL_NORESCALE      // (in this ablation build hipcc loses track of the address being wave-uniform)
-        lds = __builtin_amdgcn_readfirstlane(lds);
-#endif
         asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2"
                      :: "s"(lds), "v"(off_bytes), "s"(base) : "memory");
     };
@@ -537,57 +461,31 @@ __global__ __launch_bounds__(256, 2) void attn_vit_pipe_kernel(VitAttnArgs p) {
             dma16(kb, off[i], st + (wid + NW * i) * 1024);
             dma16(vb, off[i], st + TILE + (wid + NW * i) * 1024);
         }
-#ifdef AV_ABL_NO_NINTH       // timing experiment (tools/attn_abl.sh): what do the ninth pieces cost? (wrong results)
-#elif defined(AV_WAVE_NINTH)
-        if (wid == 0) dma16(kb, off[NPI], st + 8 * 1024);
-        if (wid == 1) dma16(vb, off[NPI], st + TILE + 8 * 1024);
-#else
         // EXEC is all ones here (wave-uniform control flow throughout the kernel) and is put back to all ones
         const unsigned long long nx = ninth_exec;                // (copies: an asm operand alone does not capture in a generic lambda)
         const bf16_t* const nb = ninth_v ? vb : kb;
-#ifdef AV_ABL_NORESCALE
-        const unsigned nl = __builtin_amdgcn_readfirstlane(st + (ninth_v ? TILE : 0) + 8 * 1024);
-#else
         const unsigned nl = st + (ninth_v ? TILE : 0) + 8 * 1024;
-#endif
         const int no = off[NPI];
         asm volatile("s_mov_b64 exec, %0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3\n\ts_mov_b64 exec, -1"
                      :: "s"(nx), "s"(nl), "v"(no), "s"(nb) : "memory");
-#endif
     };
     auto issue_tile = [&](int t, int slot) { issue_tile_g(t, slot, std::false_type{}); };      // ragged or not: tested
     using FirstTilesFull = std::integral_constant<bool, (R > 0)>;                               // R > 0: nt >= 4
-    // this wave's pieces of every tile but the `newer` most recently issued ones have landed (n_own = 2 NPI or 2 NPI + 1)
-#ifdef AV_OLD_BRANCHES      // A/B builds (tools/attn_abl.sh): the round-5 control flow of the tile loop
-    auto wait_tiles = [&](int newer) {
-        if (newer <= 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        else if (newer == 1) { if (n_own == 2 * NPI + 1) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * NPI + 1) : "memory"); else asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * NPI) : "memory"); }
-        else { if (n_own == 2 * NPI + 1) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(4 * NPI + 2) : "memory"); else asm volatile("s_waitcnt vmcnt(%0)" :: "n"(4 * NPI) : "memory"); }
-    };
-#else
-    // Round 6: ONE immediate per case for all four waves -- the count of the waves that issue 2 NPI pieces per tile. The two waves
-    // with an extra piece then also wait for the oldest piece of the next-but-one tile (issued a whole tile earlier: landed), and
-    // the tile loop loses a wave-dependent branch in front of its barrier (a scalar branch next to an MFMA block costs percent:
-    // profiles/r6_gemm_idle_branch_ab.txt, r6_prefill_attn_branches_ab.txt).
-    (void)n_own;
-#ifdef AV_WAVE_NINTH
-    constexpr int PER_TILE = 2 * NPI;
-#else
-    constexpr int PER_TILE = 2 * NPI + 1;      // every wave alike: exact
-#endif
+    // this wave's pieces of every tile but the `newer` most recently issued ones have landed. Every wave issues PER_TILE requests
+    // per tile, so ONE immediate per case serves all four waves and the tile loop has no wave-dependent branch in front of its
+    // barrier (a scalar branch next to an MFMA block costs percent: profiles/r6_gemm_idle_branch_ab.txt,
+    // r6_prefill_attn_branches_ab.txt).
+    constexpr int PER_TILE = 2 * NPI + 1;
     auto wait_tiles = [&](int newer) {
         if (newer <= 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         else if (newer == 1) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(PER_TILE) : "memory");
         else asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * PER_TILE) : "memory");
     };
-#endif
 
-#ifndef AV_LATE_ISSUE
     // Round 5: tile 0 goes out HERE, as soon as its addresses exist -- in front of the ~800 cycles of per-lane read offsets,
     // accumulator zeroing and fragment-address setup below, which then run under the memory round trip instead of in front of it
     // (inline-asm DMA is a scheduling boundary for hipcc: where the statement stands is where the instruction goes).
     issue_tile_g(0, 0, FirstTilesFull{});
-#endif
     // per-lane LDS read offsets inside a stage. K: lane (key r32, k-half h) reads 16 bytes at column 32 ks + 16 h; in
     // the last k-step half 1 is the pad chunk -> constant [1, 0 x7]
     const int k_rd = r32 * RS + h * 16;
@@ -678,12 +576,6 @@ __global__ __launch_bounds__(256, 2) void attn_vit_pipe_kernel(VitAttnArgs p) {
     // compiler's own wait for Q -- a vmcnt(0), it cannot see the DMA -- covers the tiles as well. Stamped entry of a
     // workgroup with Q waited for first: 700-1 700 cycles to the segment bounds, 800 of address setup, 1 300-1 900 for
     // Q, 3 700-4 600 for issuing three tiles and landing the first)
-#ifdef COGS_PIPE_STAMPS2
-    PSTAMP();      // Q loads issued
-#endif
-#ifdef AV_LATE_ISSUE
-    issue_tile_g(0, 0, FirstTilesFull{});
-#endif
     // round 4: only Q and tile 0 go out before the first wait (10 vector-memory instructions per wave instead of 18: the
     // CU's vector-memory path takes one 1 KiB piece per ~60-115 cycles, so the 8 pieces of tiles 1 and 2 used to stand
     // between every wave and its first MFMA); tiles 1 and 2 follow behind the barrier, in order, so the counted waits of
@@ -693,14 +585,10 @@ __global__ __launch_bounds__(256, 2) void attn_vit_pipe_kernel(VitAttnArgs p) {
         if (R > 0 || nt > 1) issue_tile_g(1, 1, FirstTilesFull{});
         if (R > 0 || nt > 2) issue_tile_g(2, 2, FirstTilesFull{});
     }
-#ifdef COGS_PIPE_STAMPS2
-    PSTAMP();      // tiles issued
-#endif
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll
     for (int s = 0; s < KS; ++s) asm volatile("" : "+v"(qf[s]));      // Q loads complete before the loop (see attn_vit_kernel)
     __builtin_amdgcn_s_waitcnt(0xc07f);                               // lgkmcnt(0): the constant chunks
-    PSTAMP();      // 1: Q and tile 0 landed
     __builtin_amdgcn_s_barrier();
     if (!EARLY) {
         if (R > 0 || nt > 1) issue_tile_g(1, 1, FirstTilesFull{});
@@ -765,11 +653,7 @@ __global__ __launch_bounds__(256, 2) void attn_vit_pipe_kernel(VitAttnArgs p) {
             // canonicalising v_max in front of every chain): 17 -> 8 vector instructions per 32-key block on the port this
             // kernel is bound by (per tile and wave: 22 MFMA x 8 issue cycles + 32 v_exp x 8 + 16 v_cvt_pk + the maxima)
             const float d_own = own_max(sn);
-#ifdef AV_ABL_NORESCALE      // timing experiment (tools/attn_abl.sh): what does the rare path's wave vote + branch cost?
-            if (false) {
-#else
             if (__any(d_own > RESCALE_THR)) {
-#endif
                 // rare (wave-uniform): move the reference of the rows that need it; O, now complete up to block j, is
                 // multiplied by 2^-(m_new - sh) and S(j+1) is simply computed again with the new shift
                 const float d = pair_max(d_own);
@@ -787,33 +671,16 @@ __global__ __launch_bounds__(256, 2) void attn_vit_pipe_kernel(VitAttnArgs p) {
             }
         }
     };
-#ifdef COGS_PHASE_STAMPS
-    unsigned long long ph_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
     // slot_tag: ring slot of tile t when known at compile time, else -1; steady_tag: tiles t + 2 and t + 3 are known to exist (the
     // unrolled main loop), so neither the wait nor the issue is behind a run-time test
     auto tile_head = [&](const int t, auto slot_tag, auto steady_tag) {
         constexpr int SLOT = decltype(slot_tag)::value;
-#ifdef AV_OLD_BRANCHES
-        constexpr bool STEADY = false;
-#else
         constexpr bool STEADY = decltype(steady_tag)::value;
-#endif
         // outstanding, oldest first: tile t+1 (if any), tile t+2 (if any); tile t+1 must have landed
-        unsigned long long h0 = 0, h1 = 0, h2 = 0, h3 = 0;
-        PHT(h0);
         if constexpr (STEADY) wait_tiles(1); else wait_tiles(t + 2 < nt ? 1 : 0);
-        PHT(h1);
         __builtin_amdgcn_s_barrier();     // K(t+1), V(t) visible to all; slot of tile t-1 no longer read by anyone
-        PHT(h2);
-#ifndef ABL_NOLOAD
         if constexpr (STEADY && R > 0) issue_tile_g(t + 3, (SLOT + 3) & (NS - 1), std::true_type{});      // a full tile by the choice of R
         else if (STEADY || t + 3 < nt) issue_tile(t + 3, SLOT >= 0 ? (SLOT + 3) & (NS - 1) : (t + 3) & (NS - 1));
-#endif
-        PHT(h3);
-#ifdef COGS_PHASE_STAMPS
-        ph_acc[0] += h1 - h0; ph_acc[1] += h2 - h1; ph_acc[2] += h3 - h2; ph_acc[3] += 1;
-#endif
     };
 
     // the same with everything decided at compile time: WAIT1 = tile t + 2 exists (it may stay in flight), ISSUE = tile t + 3 exists
@@ -823,55 +690,28 @@ __global__ __launch_bounds__(256, 2) void attn_vit_pipe_kernel(VitAttnArgs p) {
         constexpr int ISSUE = decltype(issue_tag)::value;
         if constexpr (decltype(wait1_tag)::value) wait_tiles(1); else wait_tiles(0);
         __builtin_amdgcn_s_barrier();
-#ifndef ABL_NOLOAD
         if constexpr (ISSUE == 2) issue_tile_g(t + 3, (SLOT + 3) & (NS - 1), std::true_type{});
         else if constexpr (ISSUE == 1) issue_tile(t + 3, (SLOT + 3) & (NS - 1));
-#endif
     };
-
-    PSTAMP();      // 2: S(0) ready
-#ifndef AV_OLD_BRANCHES
     // A wave whose 32 query rows all lie past the segment end (the ragged last query block) only stages and keeps the barriers: it
     // walks the tile heads here and leaves, so the waves that compute carry no `wave_active` test between a tile's barrier and its MFMAs
     if (!wave_active) {
         for (int ti = 0; ti < nt; ++ti) tile_head(ti, std::integral_constant<int, -1>{}, std::false_type{});
         return;
     }
-#endif
     int t = 0;
     using Full = std::integral_constant<int, 1>;
-#ifndef AV_NO_UNROLL4
     // four tiles per trip: t is a multiple of 4 here, so tile t + i sits in ring slot i (compile-time LDS addresses)
     // (R > 0: the trips end R tiles before the end; else: while blocks up to 2 t + 8 are full and t + 6 < nt, the tile the trip's
     // last head requests)
     for (; R > 0 ? t + R < nt : 2 * (t + 3) + 2 < nfull && t + 6 < nt; t += 4) {
-#ifdef ABL_NOCOMPUTE
-#define COGS_AV_ACTIVE false
-#elif defined(AV_OLD_BRANCHES)
-#define COGS_AV_ACTIVE wave_active
-#else
-#define COGS_AV_ACTIVE true
-#endif
-#ifdef COGS_PHASE_STAMPS
-#define COGS_PH_ADD(a_, b_, c_) ph_acc[4] += (b_) - (a_); ph_acc[5] += (c_) - (b_);
-#else
-#define COGS_PH_ADD(a_, b_, c_)
-#endif
 #define COGS_AV_TILE(I)                                                                                      \
-        tile_head(t + I, std::integral_constant<int, I>{}, std::true_type{});                                                  \
-        if (COGS_AV_ACTIVE) {                                                                                \
-            unsigned long long c0_ = 0, c1_ = 0, c2_ = 0;                                                    \
-            PHT(c0_);                                                                                        \
-            substep(sa, sb, 2 * (t + I), Full{}, std::integral_constant<int, I>{});                          \
-            PHT(c1_);                                                                                        \
-            substep(sb, sa, 2 * (t + I) + 1, Full{}, std::integral_constant<int, I>{});                      \
-            PHT(c2_);                                                                                        \
-            COGS_PH_ADD(c0_, c1_, c2_)                                                                       \
-        }
+        tile_head(t + I, std::integral_constant<int, I>{}, std::true_type{});                                \
+        substep(sa, sb, 2 * (t + I), Full{}, std::integral_constant<int, I>{});                              \
+        substep(sb, sa, 2 * (t + I) + 1, Full{}, std::integral_constant<int, I>{});
         COGS_AV_TILE(0) COGS_AV_TILE(1) COGS_AV_TILE(2) COGS_AV_TILE(3)
 #undef COGS_AV_TILE
     }
-#endif
     if constexpr (R > 0) {
         // the last R tiles, t = nt - R (a multiple of 4): tile t + I in ring slot I & 3; NB blocks in all, block E from the end is the
         // last one (KIND 0), the one in front of it computes the last block's scores under its mask (KIND 3; a full last block
@@ -896,30 +736,14 @@ __global__ __launch_bounds__(256, 2) void attn_vit_pipe_kernel(VitAttnArgs p) {
     if constexpr (R == 0)
     for (; 2 * t + 2 < nfull; ++t) {              // blocks 2t+1 and 2t+2 are full
         tile_head(t, std::integral_constant<int, -1>{}, std::false_type{});
-#ifndef ABL_NOCOMPUTE
         if (wave_active) {
             substep(sa, sb, 2 * t, Full{}, std::integral_constant<int, -1>{});
             substep(sb, sa, 2 * t + 1, Full{}, std::integral_constant<int, -1>{});
         }
-#endif
     }
-#ifdef COGS_PHASE_STAMPS
-    if (COGS_AV_LINEAR_ID == 3000 && tid == 0) { for (int i = 0; i < 8; ++i) g_attn_stamps[i] = ph_acc[i]; }
-#endif
-    PSTAMP();      // 3: main loop done
-#ifdef COGS_PHASE_STAMPS
-    unsigned long long tl_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    int tl_n = 0;
-#endif
     if constexpr (R == 0)
     for (; t < nt; ++t) {                         // the ragged end: block kinds decided at run time (wave-uniform)
-        unsigned long long q0_ = 0, q1_ = 0;
-        PHT(q0_);
         tile_head(t, std::integral_constant<int, -1>{}, std::false_type{});
-        PHT(q1_);
-#ifdef COGS_PHASE_STAMPS
-        tl_acc[0] += q1_ - q0_;
-#endif
         if (!wave_active) continue;
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) {
@@ -927,22 +751,11 @@ __global__ __launch_bounds__(256, 2) void attn_vit_pipe_kernel(VitAttnArgs p) {
             if (j >= nblk) break;
             f32x16& sc = kb == 0 ? sa : sb;
             f32x16& sn = kb == 0 ? sb : sa;
-            unsigned long long u0_ = 0, u1_ = 0;
-            PHT(u0_);
             if (j + 1 < nfull) substep(sc, sn, j, Full{}, std::integral_constant<int, -1>{});
             else if (j + 1 < nblk) substep(sc, sn, j, std::integral_constant<int, 3>{}, std::integral_constant<int, -1>{});
             else substep(sc, sn, j, std::integral_constant<int, 0>{}, std::integral_constant<int, -1>{});
-            PHT(u1_);
-#ifdef COGS_PHASE_STAMPS
-            if (tl_n < 6) tl_acc[1 + tl_n] = u1_ - u0_;
-            ++tl_n;
-#endif
         }
     }
-#ifdef COGS_PHASE_STAMPS
-    if (COGS_AV_LINEAR_ID == 3000 && tid == 0) { for (int i = 0; i < 8; ++i) g_tail_stamps[i] = tl_acc[i]; }
-#endif
-    PSTAMP();      // 4: tail done
     if (!wave_active) return;
 
     constexpr int LB = HD / 32, LR = HD % 32;
@@ -966,13 +779,6 @@ __global__ __launch_bounds__(256, 2) void attn_vit_pipe_kernel(VitAttnArgs p) {
             if (qok && d0 < HD) *reinterpret_cast<u32x4*>(orow + d0) = u32x4{(unsigned)s0[0], (unsigned)s1[0], (unsigned)s0[1], (unsigned)s1[1]};
         }
     }
-    LIFE_NOW(life1);
-    LIFE_ADD(0, life1 - life0); LIFE_ADD(1, 1);
-#ifdef COGS_PIPE_STAMPS
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    PSTAMP();      // 5: O stored
-    if (COGS_AV_LINEAR_ID == 3000 && tid == 0) { for (int i = 0; i < 8; ++i) g_attn_stamps[i] = ps_t[i]; }
-#endif
 }
 
 }  // namespace

@@ -171,12 +171,6 @@ __device__ __forceinline__ float gelu_tanh_f(float x) {
 __device__ __forceinline__ f32x4 gelu_tanh_4(f32x4 x) {
     const float a = -2.3022082f, b = -0.10294324f;
     const f32x4 a4 = {a, a, a, a}, b4 = {b, b, b, b}, one = {1.f, 1.f, 1.f, 1.f};
-#ifdef COGS_EPI_SCALAR_MATH      // A/B builds (tools/build_alt.sh gemm -DCOGS_EPI_SCALAR_MATH): the scalar form of rounds 1-4
-    f32x4 y;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) y[e] = gelu_tanh_f(x[e]);
-    return y;
-#endif
     const f32x4 t = x * __builtin_elementwise_fma(b4, x * x, a4);
     f32x4 d;
 #pragma unroll

@@ -28,7 +28,7 @@
     X(gemm_ring_cost_permille, 720, "few-tile choice: cost of a round of ring tiles relative to a round of ping-pong tiles") \
     X(gemm_epi_serial, 0, "1: the two wave groups' epilogues in separate intervals (the order before round 4)")             \
     X(gemm_nostore, 0, "1: timing only -- K loops without epilogues (results are NOT written)")                             \
-    X(gemm_trace, 0, "1: per-tile s_memtime stamps of workgroup 0 printed to stderr (synchronises)")                        \
+    X(gemm_trace, 0, "1: per-tile s_memtime stamps of workgroup 0 printed to stderr (K-tile body only; synchronises)")      \
     X(gemm_choice, 0, "1: print which body every ping-pong-eligible shape gets")                                            \
     X(gemm_headmajor, 1, "ViT encode: QKV GEMM writes q/k/v head-major [which][head][row][hd] for the attention kernel")    \
     X(gemv_small_n, 1024, "GEMV: 2 output rows per wave while N / 16 is below this (else 4)") \

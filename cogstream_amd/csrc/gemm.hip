@@ -48,7 +48,7 @@ struct GemmArgs {
     int cf;                      // whole-line ping-pong kernel: tiles of a FULL group = group_m * nbn (+ its tall tiles: see TALL4)
     int ntiles;                  //   ... and the tiles of the whole launch
     int epi_serial;              // whole-line kernel, A/B runs (debug switch gemm_epi_serial): both groups' epilogues behind the tile's last barrier
-    unsigned long long* trace;   // diagnostics (debug switch gemm_trace): per-tile s_memtime stamps of WG 0, waves 0 and 4
+    unsigned long long* trace;   // diagnostics (debug switch gemm_trace, K-tile body only): per-tile s_memtime stamps of WG 0, waves 0 and 4
     EpiArgs epi;
 };
 
@@ -364,7 +364,7 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_256x128_kernel(GemmArgs p) {
 // and group 1 runs ONE BARRIER BEHIND group 0, so on every SIMD one wave is in its C segment while the
 // other is in its L segment. Persistent over tiles with a continuous K-tile stream (prefetch distance 3 K-tiles, one
 // counted vmcnt per K-tile). The first version cut a K-tile into two such L/C pairs (upper / lower 64 rows: 16 fewer
-// fragment registers); interval stamps (-DCOGS_GEMM_KSTAMPS build, tools/gemm_trace.py) put its L segments at 330-440
+// fragment registers); interval stamps (profiles/r4_gemm_kstamps.txt) put its L segments at 330-440
 // cycles against 258 for 16 MFMAs, and with the staging thinned out (timing experiments) an interval still took
 // ~100 cycles more than its MFMAs: the hand-over between the groups costs about as much as the imbalance. One pair
 // per K-tile halves the hand-overs: -3..-6 % on every shape but one (in-run A/B: fc1+GELU 0.588 -> 0.569 ms,
@@ -520,14 +520,6 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_pp_kernel(GemmArgs p) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) acc[h][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
         stamp();
-#ifdef COGS_GEMM_KSTAMPS
-        // diagnostic build only: where does an interval go? sums over the K-tiles of this tile, per wave group
-        unsigned long long ks_L0 = 0, ks_W0 = 0, ks_C0 = 0, ks_X0 = 0;
-        unsigned long long ks_prev = __builtin_amdgcn_s_memtime();
-#define KSTAMP(acc_) do { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); acc_ += now_ - ks_prev; ks_prev = now_; } while (0)
-#else
-#define KSTAMP(acc_) do {} while (0)
-#endif
         for (int kt = 0; kt < KT; ++kt, ++g) {
             const char* base = smem + slot * SLOT3;
             // ---- L segment: the K-tile's 12 fragment reads and this wave's 4 staging pieces ----
@@ -552,9 +544,7 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_pp_kernel(GemmArgs p) {
             // group 1 here (end of its L segment), group 0 at the end of its C segment below.
             const int ahead = total - 1 - g;   // K-tiles after the current one
             if (grp == 1) wait_next_ktile(ahead, kt);
-            KSTAMP(ks_L0);
             __builtin_amdgcn_s_barrier();
-            KSTAMP(ks_W0);
             // ---- C segment: 32 MFMAs (upper, then lower 64 rows of the wave's tile) ----
             __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -571,20 +561,12 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_pp_kernel(GemmArgs p) {
                         __builtin_bit_cast(bf16x8, wfr[ni]), __builtin_bit_cast(bf16x8, afr2[mi]), acc[1][mi][ni], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
             if (grp == 0) wait_next_ktile(ahead, kt);
-            KSTAMP(ks_C0);
             __builtin_amdgcn_s_barrier();
-            KSTAMP(ks_X0);
             __builtin_amdgcn_sched_barrier(0);
             __builtin_amdgcn_s_setprio(0);
             asm volatile("" ::: "memory");
             slot = slot + 1 == RING3 ? 0 : slot + 1;
         }
-#ifdef COGS_GEMM_KSTAMPS
-        if (tracing && lane == 0 && t == (int)blockIdx.x) {   // first tile of workgroup 0
-            unsigned long long* o = p.trace + 192 + grp * 8;
-            o[0] = ks_L0; o[1] = ks_W0; o[2] = ks_C0; o[3] = ks_X0; o[4] = o[5] = o[6] = o[7] = 0;
-        }
-#endif
         // epilogue of this tile; it runs inside this group's next L interval, i.e. beside the other group's C
         stamp();
         stamp();
@@ -797,28 +779,15 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_pp64_kernel(GemmArgs p) {
             m0 += rg * 128;
             n0 += cg * 64;
         }
-#ifdef COGS_GEMM_TSTAMPS     // diagnostic build (tools/gemm_trace.py): K loop / tile boundary of workgroup 0, waves 0 and 4, per tile
-        const bool ts_on = p.trace && blockIdx.x == 0 && wc == 0;
-        const int ts_i = (t - (int)blockIdx.x) / (int)gridDim.x;
-        if (ts_on && ts_i < 24) { const unsigned long long tm_ = __builtin_amdgcn_s_memtime(); if (lane == 0) p.trace[grp * 96 + 4 * ts_i] = tm_; }
-#endif
 #pragma unroll
         for (int h = 0; h < 2; ++h)
 #pragma unroll
             for (int i = 0; i < 4; ++i)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) acc[h][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-#ifdef COGS_GEMM_KSTAMPS
-        // diagnostic build only: where does a slab's time go? sums over the slabs of this tile, per wave group
-        unsigned long long ks_sum[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        unsigned long long ks_prev = __builtin_amdgcn_s_memtime();
-#define KSTAMP4(i_) do { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); ks_sum[i_] += now_ - ks_prev; ks_prev = now_; } while (0)
-#else
-#define KSTAMP4(i_) do {} while (0)
-#endif
         // One slab. STEADY = a slab that is neither the first of its tile nor one of the stream's last two: its wait is
         // always vmcnt(4), written without a single scalar instruction behind the MFMAs of C1. Measured with interval stamps
-        // (-DCOGS_GEMM_KSTAMPS build): whatever DECIDES at that point -- the compiler's lane-mask conversion (v_cndmask /
+        // (profiles/r4_gemm_kstamps.txt): whatever DECIDES at that point -- the compiler's lane-mask conversion (v_cndmask /
         // v_cmp writing an SGPR) or a tree of s_cmp / taken s_cbranch on a pinned SGPR -- costs 180-340 cycles per slab
         // there, against 4 cycles for nothing. Group 1, whose wait stands at the end of L1, executes the C1 wait too: by
         // then it has at most A(g+2) outstanding, so it falls through. The other slabs take the general form, with the
@@ -860,9 +829,7 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_pp64_kernel(GemmArgs p) {
                     if constexpr (STEADY) { if (is_g1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); }
                     else wait_next_slab(wm_l1);
                 }
-                KSTAMP4(half * 6 + 0);
                 __builtin_amdgcn_s_barrier();
-                KSTAMP4(half * 6 + 1);
                 // ---- C segment: 32 MFMAs. (The two waves a tall tile leaves without a region run them too, on whatever their
                 // fragment reads returned, and drop the result: a run-time `if (!idle)` here -- one scalar branch in front of every
                 // MFMA block -- cost EVERY GEMM 2-6 % (profiles/r6_gemm_idle_branch_ab.txt), and the same choice made once per
@@ -875,11 +842,6 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_pp64_kernel(GemmArgs p) {
                     for (int ni = 0; ni < 4; ++ni)
                         acc[0][mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
                             __builtin_bit_cast(bf16x8, wfr[ni]), __builtin_bit_cast(bf16x8, afr[mi]), acc[0][mi][ni], 0, 0, 0);
-#ifdef COGS_GEMM_KSTAMPS
-                __builtin_amdgcn_sched_barrier(0);
-                KSTAMP4(half * 6 + 2);
-                __builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
                 for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
@@ -888,14 +850,11 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_pp64_kernel(GemmArgs p) {
                             __builtin_bit_cast(bf16x8, wfr[ni]), __builtin_bit_cast(bf16x8, afr2[mi]), acc[1][mi][ni], 0, 0, 0);
                 }
                 __builtin_amdgcn_sched_barrier(0);
-                KSTAMP4(half * 6 + 3);
                 if (half == 1) {
                     if constexpr (STEADY) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
                     else wait_next_slab(wm_c1);
                 }
-                KSTAMP4(half * 6 + 4);
                 if (!(LAST && half == 1)) __builtin_amdgcn_s_barrier();
-                KSTAMP4(half * 6 + 5);
                 __builtin_amdgcn_sched_barrier(0);
                 __builtin_amdgcn_s_setprio(0);
                 asm volatile("" ::: "memory");
@@ -912,28 +871,16 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_pp64_kernel(GemmArgs p) {
         for (; ks < KS - 1; ++ks, ++g) slab(std::false_type{}, std::false_type{}, ks);
         slab(std::false_type{}, std::true_type{}, ks);
         ++ks; ++g;
-#ifdef COGS_GEMM_KSTAMPS
-        if (p.trace && blockIdx.x == 0 && wc == 0 && lane == 0 && t == (int)blockIdx.x) {   // first tile of workgroup 0
-            unsigned long long* o = p.trace + 192 + grp * 12;
-            for (int i = 0; i < 12; ++i) o[i] = ks_sum[i];
-        }
-#endif
         // Tile end. The barrier that closes the last slab stands BEFORE group 0's epilogue and BEHIND group 1's, so the
         // two epilogues share one interval (group 0: epilogue + first load segment of the next tile; group 1: its last
         // MFMA segment + epilogue) instead of taking one each while the other group waits at a barrier.
         // W of the next tile's second slab goes out in front of the epilogue, into the position of this tile's last A
         // unit: a wave stages rows 32w..32w+31 of it, rows that only its own group read (before this point).
-#ifdef COGS_GEMM_TSTAMPS
-        if (ts_on && ts_i < 24) { const unsigned long long tm_ = __builtin_amdgcn_s_memtime(); if (lane == 0) { p.trace[grp * 96 + 4 * ts_i + 1] = tm_; p.trace[grp * 96 + 4 * ts_i + 2] = tm_; } }
-#endif
         if (grp == 0 || p.epi_serial) __builtin_amdgcn_s_barrier();
         issue_w();
         pre_issued = true;
         int ops = -2;      // -2: this wave had no region (tall tile) and issued nothing
         if (!idle) ops = epilogue_wave_pair<T, EPI>(p.epi, m0, n0, p.M, p.N, lane, acc[0], acc[1]);
-#ifdef COGS_GEMM_TSTAMPS
-        if (ts_on && ts_i < 24) { const unsigned long long tm_ = __builtin_amdgcn_s_memtime(); if (lane == 0) p.trace[grp * 96 + 4 * ts_i + 3] = tm_; }
-#endif
         if (grp == 1 && !p.epi_serial) __builtin_amdgcn_s_barrier();
 #ifdef COGS_EPI_CONSERVATIVE
         epi_ops = ops == -2 ? -2 : 0;
@@ -969,7 +916,8 @@ void launch_big(hipStream_t st, const GemmArgs& p, const GemmLaunch& l) {
     cogs_ensure_dyn_lds((const void*)gemm_tn_256x128_kernel<T, EPI>, (int)lds, attr_done);
     hipLaunchKernelGGL((gemm_tn_256x128_kernel<T, EPI>), dim3(l.grid), dim3(512), lds, st, p);
 }
-// debug switch gemm_trace: the same launch with a stamp buffer, then the per-tile stamps of workgroup 0 on stderr (synchronises)
+// debug switch gemm_trace: the same launch with a stamp buffer, then the per-tile stamps of workgroup 0 on stderr (synchronises).
+// Only the K-tile body (gemm_tn_pp_kernel) writes stamps; the whole-line body leaves the buffer empty and no stamps are printed for it.
 template <typename Launch>
 void traced_launch(hipStream_t st, const GemmArgs& p, const GemmLaunch& l, int epi, Launch&& launch) {
     static unsigned long long* dbuf = nullptr;
@@ -988,21 +936,6 @@ void traced_launch(hipStream_t st, const GemmArgs& p, const GemmLaunch& l, int e
                     h[g * 96 + i + 3] - h[g * 96 + i + 2], (i + 4 < 96 && h[g * 96 + i + 4]) ? h[g * 96 + i + 4] - h[g * 96 + i + 3] : 0ull);
         fprintf(stderr, "\n");
     }
-#ifdef COGS_GEMM_KSTAMPS
-    for (int g = 0; g < 2; ++g) {
-        const unsigned long long* o = h + 192 + g * 8;
-        const double kt_n = p.K / 32.0;
-        if (l.body == 4) {
-            const unsigned long long* q = h + 192 + g * 12;
-            const double sl = kt_n / 2;
-            fprintf(stderr, "[gemm kstamps] group %d per 64-wide slab: L0 %.0f wait %.0f C0 %.0f+%.0f vm %.0f wait %.0f | L1 %.0f wait %.0f C1 %.0f+%.0f vm %.0f wait %.0f\n",
-                    g, q[0] / sl, q[1] / sl, q[2] / sl, q[3] / sl, q[4] / sl, q[5] / sl, q[6] / sl, q[7] / sl, q[8] / sl, q[9] / sl, q[10] / sl, q[11] / sl);
-        }
-        else
-        fprintf(stderr, "[gemm kstamps] group %d per K-tile: L %.0f wait %.0f C %.0f wait %.0f\n",
-                g, o[0] / kt_n, o[1] / kt_n, o[2] / kt_n, o[3] / kt_n);
-    }
-#endif
 }
 // the ping-pong bodies: 4 the whole-line kernel, 3 the K-tile kernel (the only one with the rotary LUT epilogue)
 template <int EPI>

@@ -611,12 +611,7 @@ __device__ __forceinline__ void epilogue_pair_fast(const EpiArgs& p, int mb, int
                 v[h2] = (blk < 4) ? acc0[mi][ni] : acc1[mi][ni];
                 if constexpr ((EPI & EPI_LNFOLD) != 0) {
                     const float rs = rs_ring[UPB == 1 ? (blk & 7) : blk];
-#ifdef COGS_EPI_SCALAR_MATH
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[h2][e] = fmaf(rs, v[h2][e], bias_v[ni][e]);
-#else
                     v[h2] = __builtin_elementwise_fma(f32x4{rs, rs, rs, rs}, v[h2], bias_v[ni]);
-#endif
                 } else if constexpr ((EPI & EPI_BIAS) != 0) v[h2] += bias_v[ni];
                 if constexpr ((EPI & EPI_ROPE) != 0) {
                     const f32x4 t = cs4[b][j][h2];   // c0 s0 c1 s1
@@ -713,9 +708,7 @@ __device__ __forceinline__ void epilogue_pair_fast(const EpiArgs& p, int mb, int
     constexpr bool HAS_LOADS = (EPI & (EPI_RES | EPI_ROPE | EPI_LNFOLD)) != 0;
     // batches in flight: 2, or -- rotary (1-unit batches of two 16-byte table loads: round 6's tile stamps put a rotary tile's
     // epilogue at 15.5 k cycles against 5 k for a plain one, sixteen load round trips two at a time) -- COGS_ROPE_DEPTH
-#ifndef COGS_ROPE_DEPTH
-#define COGS_ROPE_DEPTH 4
-#endif
+    constexpr int COGS_ROPE_DEPTH = 4;
     constexpr int DEPTH = (EPI & EPI_ROPE) != 0 ? COGS_ROPE_DEPTH : 2;
     if constexpr (HAS_LOADS) {
 #pragma unroll

@@ -13,12 +13,7 @@
 
 // 16-byte chunks per row in flight per lane (R * U = 8 loads); swept with tools/micro/gemv_micro.cpp: (2 rows, U 4) and
 // (4 rows, U 2) are the fastest or level on every decode shape (U 7 / 8 / 3 / 4: within +-4 %, each slower somewhere)
-#ifndef GEMV_U_SMALL
-#define GEMV_U_SMALL 4
-#endif
-#ifndef GEMV_U_BIG
-#define GEMV_U_BIG 2
-#endif
+constexpr int GEMV_U_SMALL = 4, GEMV_U_BIG = 2;
 
 namespace {
 
@@ -129,13 +124,9 @@ __global__ __launch_bounds__(256) void gemv_kernel(GemvArgs p) {
         }
     };
     // Weights are read exactly once per token by exactly one CU: non-temporal loads keep them from displacing what IS
-    // re-read (x, the KV cache, the next kernels' operands) in L2 / the Infinity Cache (A/B: build with -DCOGS_GEMV_NO_NT)
+    // re-read (x, the KV cache, the next kernels' operands) in L2 / the Infinity Cache (A/B against plain loads: gate/up 47.5 -> 43.0 us, DESIGN_HISTORY.md)
     auto ldw = [](const T* q) -> u32x4 {
-#ifndef COGS_GEMV_NO_NT
         return __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(q));
-#else
-        return *reinterpret_cast<const u32x4*>(q);
-#endif
     };
     // The first batch of weight chunks is requested BEFORE the fused RMSNorm statistics: the weights do not depend
     // on x, and the statistics (a dependent load -> reduce -> rsqrt chain, ~2 us) would otherwise sit in front of the

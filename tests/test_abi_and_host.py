@@ -58,6 +58,24 @@ def test_product_does_not_import_oracle():
                 assert not re.search(r"^\s*(from|import)\s+oracle\b", src, re.M), f"{f} imports the oracle"
 
 
+def test_kernel_sources_have_no_experiment_conditionals():
+    """what csrc/ holds is what reaches the GPU: the only conditional compilation is the two build fallbacks that
+    cogstream_amd/build.py and the nopair A/B test use"""
+    import glob
+    csrc = os.path.join(ROOT, "cogstream_amd", "csrc")
+    files = sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h")))
+    assert len(files) >= 20
+    named = {}
+    for path in files:
+        for line in open(path).read().replace("\\\n", " ").splitlines():      # continuation lines joined
+            m = re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b(.*)", line)
+            if m:
+                idents = set(re.findall(r"[A-Za-z_]\w*", m.group(2).split("//")[0])) - {"defined"}
+                for ident in idents or {line.strip()}:      # a condition that names nothing (#if 0) is reported as it stands
+                    named.setdefault(ident, os.path.basename(path))
+    assert set(named) <= {"COGS_EPI_CONSERVATIVE", "COGS_EPI_NOPAIR"}, named
+
+
 def test_resize_table_and_patchify():
     """size table of SURVEY.md section 8 (computed from image_processing_videollama3.py:93-131)"""
     from cogstream_amd import processing as pr

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-tile cycle stamps of the ping-pong GEMM (debug switch gemm_trace): K-loop / epilogue cycles of workgroup 0."""
+"""Per-tile cycle stamps of the ping-pong GEMM's K-tile body (debug switch gemm_trace): K-loop / epilogue cycles of workgroup 0."""
 import os
 import sys
 

@@ -1,5 +1,5 @@
-// Stand-alone timing / stamp harness for csrc/attn_vit.hip (ViT block-diagonal attention, hd 72):
-//   hipcc -O3 -std=c++17 --offload-arch=gfx950 [-DCOGS_ATTN_STAMPS] -I cogstream_amd/csrc tools/micro/attn_vit_micro.cpp -o tools/micro/attn_vit_micro
+// Stand-alone timing harness for csrc/attn_vit.hip (ViT block-diagonal attention, hd 72):
+//   hipcc -O3 -std=c++17 --offload-arch=gfx950 -I cogstream_amd/csrc tools/micro/attn_vit_micro.cpp -o tools/micro/attn_vit_micro
 //   attn_vit_micro [frames] [rows per frame] [layout: 0 token-major fused qkv, 1 head-major q | k | v]
 #include "../../cogstream_amd/csrc/attn_vit.hip"
 CogsDebug g_cogs_debug;
@@ -51,45 +51,5 @@ int main(int argc, char** argv) {
     }
     const double fl = 4.0 * nseg * heads * (double)seg * seg * hd;
     printf("attn_vit %dx%d: mean %.4f ms min %.4f ms  %.1f TFLOP/s (min)\n", nseg, seg, sum / 20, best, fl / best / 1e9);
-#ifdef COGS_LIFE_STAMPS
-    {
-        unsigned long long lf[8];
-        hipMemcpyFromSymbol(lf, HIP_SYMBOL(g_av_life), sizeof(lf));
-        printf("workgroup lifetime (wave 0, s_memtime ticks): %.0f on average over %llu workgroups\n", lf[1] ? (double)lf[0] / lf[1] : 0.0, lf[1]);
-    }
-#endif
-#ifdef COGS_ATTN_STAMPS
-    unsigned long long st[8];
-    hipMemcpyFromSymbol(st, HIP_SYMBOL(g_attn_stamps), sizeof(st));
-    const double n = (double)st[5];
-    printf("per full tile, wave 0 of one workgroup (cycles): barrier wait %.0f | stage %.0f | QK (to results) %.0f | softmax %.0f | PV issue %.0f | sum %.0f\n",
-           st[0] / n, st[1] / n, st[2] / n, st[3] / n, st[4] / n, (st[0] + st[1] + st[2] + st[3] + st[4]) / n);
-#endif
-#ifdef COGS_PHASE_STAMPS
-    {
-        unsigned long long st[8];
-        hipMemcpyFromSymbol(st, HIP_SYMBOL(g_attn_stamps), sizeof(st));
-        const double n = (double)st[3] + 1e-9;
-        printf("workgroup 3000, wave 0, %d main-loop tiles, shader cycles per tile: wait for tile t+1 %.0f | barrier %.0f | issue of tile t+3 %.0f | sub-step 0 %.0f | sub-step 1 %.0f | sum %.0f\n",
-               (int)n, st[0] / n, st[1] / n, st[2] / n, st[4] / n, st[5] / n, (st[0] + st[1] + st[2] + st[4] + st[5]) / n);
-        unsigned long long tl[8];
-        hipMemcpyFromSymbol(tl, HIP_SYMBOL(g_tail_stamps), sizeof(tl));
-        printf("   the ragged end of the same wave (cycles): tile heads (wait + barrier + issue) %llu in all | sub-steps in order: %llu %llu %llu %llu %llu\n",
-               tl[0], tl[1], tl[2], tl[3], tl[4], tl[5]);
-    }
-#endif
-#ifdef COGS_PIPE_STAMPS
-    {
-        unsigned long long st[8];
-        hipMemcpyFromSymbol(st, HIP_SYMBOL(g_attn_stamps), sizeof(st));
-#ifdef COGS_PIPE_STAMPS2
-        printf("workgroup 3000, wave 0 (shader cycles): entry->segment bounds %llu | ->Q loads issued %llu | ->3 tiles issued %llu | ->Q and tiles landed %llu | ->S(0) ready %llu | main loop %llu | tail %llu\n",
-               st[1] - st[0], st[2] - st[1], st[3] - st[2], st[4] - st[3], st[5] - st[4], st[6] - st[5], st[7] - st[6]);
-#else
-        printf("workgroup 3000, wave 0 (shader cycles): entry->Q and tile 0 landed %llu | ->S(0) ready %llu | main loop %llu | tail %llu | epilogue+store %llu\n",
-               st[1] - st[0], st[2] - st[1], st[3] - st[2], st[4] - st[3], st[5] - st[4]);
-#endif
-    }
-#endif
     return 0;
 }

@@ -1,5 +1,5 @@
-// Phase stamps of the sampler's merge kernel (csrc/sample.hip):
-//   hipcc -O3 -std=c++17 --offload-arch=gfx950 -DCOGS_SAMPLE_STAMPS -I cogstream_amd/csrc tools/micro/sample_micro.cpp -o tools/micro/sample_micro
+// Time per call of the sampler (slice top-k + merge, csrc/sample.hip):
+//   hipcc -O3 -std=c++17 --offload-arch=gfx950 -I cogstream_amd/csrc tools/micro/sample_micro.cpp -o tools/micro/sample_micro
 #include "../../cogstream_amd/csrc/sample.hip"
 #include <cstdio>
 #include <random>
@@ -21,11 +21,5 @@ int main() {
         float ms; hipEventElapsedTime(&ms, e0, e1); if (rep && ms < best) best = ms;
     }
     printf("cogs_sample (slice top-k + merge): %.1f us per call\n", best / 20 * 1e3);
-#ifdef COGS_SAMPLE_STAMPS
-    unsigned long long st[8];
-    hipMemcpyFromSymbol(st, HIP_SYMBOL(g_sample_stamps), sizeof(st));
-    printf("merge kernel, thread 0 (shader cycles): prefilter %llu | compaction %llu | ranks %llu | ties %llu | exp + draws %llu | serial tail %llu\n",
-           st[1] - st[0], st[2] - st[1], st[3] - st[2], st[4] - st[3], st[5] - st[4], st[6] - st[5]);
-#endif
     return 0;
 }
