@@ -155,6 +155,8 @@ class AttnRowsDesc(C.Structure):
         ("O", c_void_p),
         ("rows", c_int), ("hq", c_int), ("hkv", c_int), ("head_dim", c_int),
         ("nsplit", c_int), ("ws", c_void_p), ("ws_bytes", c_size_t),
+        ("tail_slot", c_void_p),
+        ("tail_slot_ld", c_int64),
     ]
 
 
@@ -180,6 +182,12 @@ SIGNATURES = {
     "cogs_attention_rows": (c_int, [c_void_p, C.POINTER(AttnRowsDesc)]),
     "cogs_llm_decode_rows_workspace_bytes": (c_int, [c_void_p, c_int, c_int, C.POINTER(c_size_t)]),
     "cogs_llm_decode_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int, C.POINTER(KVRows), c_void_p, c_void_p, c_size_t]),
+    "cogs_llm_decode_rows_slots": (c_int, [c_void_p, c_void_p, c_void_p, c_int, C.POINTER(KVRows), c_void_p, c_void_p, c_void_p,
+                                           c_size_t]),
+    "cogs_beam_topk_workspace_bytes": (c_int, [c_int, c_int, c_int, C.POINTER(c_size_t)]),
+    "cogs_beam_topk": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                               c_size_t]),
+    "cogs_sub_rows": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p]),
     "cogs_gemv_fp8": (c_int, [c_void_p, C.POINTER(GemvFp8Desc)]),
     "cogs_quantize_fp8_rows": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p,
                                        c_int64]),

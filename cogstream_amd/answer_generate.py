@@ -287,8 +287,15 @@ def main(argv=None) -> int:
     ap.add_argument("--num_return_sequences", type=int, default=1,
                     help="N > 1: N sampled answers per question from one prefill (lockstep decode); every record gets a `responses` "
                          "list beside `prediction` (= the first of them)")
+    ap.add_argument("--num_beams", type=int, default=1,
+                    help="B > 1 (at most 16): beam search instead of sampling; with --num_return_sequences N <= B the N best "
+                         "hypotheses go into `responses`")
+    ap.add_argument("--length_penalty", type=float, default=1.0, help="--num_beams: exponent of the hypothesis length in its score")
+    ap.add_argument("--early_stopping", action="store_true", help="--num_beams: stop as soon as B hypotheses are finished")
     args = ap.parse_args(argv)
-    if args.num_return_sequences > 1 and args.greedy:
+    if args.num_beams > 1 and args.num_return_sequences > args.num_beams:
+        ap.error("--num_return_sequences has to be smaller or equal to --num_beams")
+    if args.num_beams <= 1 and args.num_return_sequences > 1 and args.greedy:
         ap.error("--num_return_sequences needs sampling (drop --greedy)")
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -311,6 +318,9 @@ def main(argv=None) -> int:
     gen = {"do_sample": False} if args.greedy else {}
     if args.num_return_sequences > 1:
         gen["num_return_sequences"] = args.num_return_sequences
+    if args.num_beams > 1:
+        gen.update(do_sample=False, num_beams=args.num_beams, length_penalty=args.length_penalty,
+                   early_stopping=args.early_stopping)
     if shard:
         model.enable_sharded_encoder(rank, world, payload=args.payload)
         if args.spread_events:

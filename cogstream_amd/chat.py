@@ -668,7 +668,9 @@ class CogReasoner:
                  new_attention_mask=None, selection_module_output="", if_visual=True, video_keys=None, **kwargs):
         """:753-807 -> (new token ids [1, n], selection_module_output). num_return_sequences = N > 1 (forwarded to
         GenerationMixin.generate by the reference's **kwargs, :802-807): [N, L] int64, rows that stopped early right-padded
-        with the generation config's pad_token_id (or the keyword's), as transformers returns them."""
+        with the generation config's pad_token_id (or the keyword's), as transformers returns them. num_beams = B > 1 (with
+        length_penalty, early_stopping; keywords or generation config, do_sample must be off): beam search, the
+        num_return_sequences <= B best hypotheses, best first."""
         for k in ("input_ids", "past_key_values", "attention_mask", "position_ids", "tokenizer", "hist_qs", "hist_as",
                   "current_question", "original_text"):
             kwargs.pop(k, None)
@@ -695,6 +697,11 @@ class CogReasoner:
                                                             "sampler", "seed")})
         eos = g.get("eos_token_id", [])
         eos = [eos] if isinstance(eos, int) else list(eos)
+        beams = {}
+        if int(kwargs.get("num_beams", g.get("num_beams", 1)) or 1) != 1:
+            beams = dict(num_beams=int(kwargs.get("num_beams", g.get("num_beams"))),
+                         length_penalty=float(kwargs.get("length_penalty", g.get("length_penalty", 1.0))),
+                         early_stopping=kwargs.get("early_stopping", g.get("early_stopping", False)))
         new = self.llm.generate(embeds, max_new_tokens=int(kwargs.get("max_new_tokens", 1024)), eos_token_id=eos,
                                 stage_times=self.stage_times,
                                 do_sample=bool(g.get("do_sample", False)), temperature=float(g.get("temperature", 1.0)),
@@ -702,7 +709,8 @@ class CogReasoner:
                                 repetition_penalty=float(g.get("repetition_penalty", 1.0)), generator=g.get("generator"),
                                 sampler=g.get("sampler", "device"), seed=g.get("seed"),
                                 prefix=self._prefix_slot("answer"),
-                                num_return_sequences=int(kwargs.get("num_return_sequences", g.get("num_return_sequences", 1)) or 1))
+                                num_return_sequences=int(kwargs.get("num_return_sequences", g.get("num_return_sequences", 1)) or 1),
+                                **beams)
         if new and isinstance(new[0], list):                    # N rows
             from .llm import pad_rows
             pad = kwargs.get("pad_token_id", g.get("pad_token_id"))

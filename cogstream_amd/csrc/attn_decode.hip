@@ -35,6 +35,9 @@ struct DecodeAttnArgs {
     const bf16_t* tail_k; const bf16_t* tail_v;
     long ldq, tail_ld, tail_row;   // elements: Q row stride, tail key stride, tail stride between rows
     int rows, ntile, tail_len;     // ntile = ceil(rows * gsz / 16) column tiles per kv head
+    // SLOT: key j of row r's tail is read from tail slot tail_slot[r * tail_slot_ld + j] (beam search: a row continues another
+    // row's tail without copying it)
+    const int* tail_slot; long tail_slot_ld;
 };
 
 // max / sum over the four lanes {li, li+16, li+32, li+48} (one query column), result in all four (see attn.hip)
@@ -56,7 +59,10 @@ __device__ __forceinline__ float col_sum4(float x) {
 // c % gsz of row c / gsz, a row's heads may straddle two tiles -- and workgroup x < nsplit * ntile runs split x % nsplit of
 // the shared keys for tile x / nsplit; workgroup nsplit * ntile + r runs row r's own tail as ONE more partial (index nsplit)
 // of that row's gsz columns. Partials are [nsplit + 1][rows * hq] slots: the combine kernel sees rows * hq heads.
-template <bool ROWS>
+// SLOT (ROWS only): the tail workgroup forms every key row's address from the row's slot table -- key j at slot s[j] * tail_row +
+// j * tail_ld -- where it otherwise adds one row base; an entry outside [0, rows) is clamped (it then reads some row's tail, never
+// outside the buffers). The shared-prefix workgroups are the ROWS ones.
+template <bool ROWS, bool SLOT = false>
 __global__ __launch_bounds__(256, 1) void attn_decode_kernel(DecodeAttnArgs p) {
     constexpr int HD = 128, VRS = 288, VT = 64 * VRS;
     __shared__ __attribute__((aligned(16))) char vs[4 * VT];          // one V tile per wave
@@ -73,6 +79,7 @@ __global__ __launch_bounds__(256, 1) void attn_decode_kernel(DecodeAttnArgs p) {
     long ldk = p.ldk, ldv = p.ldv;
     long qoff = (long)(kvh * gsz + li) * HD;                     // this lane's query column: element offset in Q ...
     int oslot = kvh * gsz + li;                                  // ... and its (row, head) slot inside one partial
+    const int* srow = nullptr;                                   // SLOT, tail workgroup: this row's slot table
     if constexpr (ROWS) {
         const int shared_blocks = p.nsplit * p.ntile;
         if ((int)blockIdx.x < shared_blocks) {
@@ -85,7 +92,8 @@ __global__ __launch_bounds__(256, 1) void attn_decode_kernel(DecodeAttnArgs p) {
         } else {
             const int row = blockIdx.x - shared_blocks;
             split = 0; nsplit = 1; part = p.nsplit; kend = p.tail_len;
-            Kp = p.tail_k + (long)row * p.tail_row; Vp = p.tail_v + (long)row * p.tail_row;
+            if constexpr (SLOT) { Kp = p.tail_k; Vp = p.tail_v; srow = p.tail_slot + (long)row * p.tail_slot_ld; }
+            else { Kp = p.tail_k + (long)row * p.tail_row; Vp = p.tail_v + (long)row * p.tail_row; }
             ldk = ldv = p.tail_ld;
             qoff = (long)row * p.ldq + (long)(kvh * gsz + li) * HD;
             oslot = row * p.hq + kvh * gsz + li;
@@ -126,14 +134,18 @@ __global__ __launch_bounds__(256, 1) void attn_decode_kernel(DecodeAttnArgs p) {
         u32x4 kf[4][4], vreg[16];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            const long ro = (long)min(16 * u + li, nvalid - 1) * ldk;
+            const int kr = min(16 * u + li, nvalid - 1);
+            long ro = (long)kr * ldk;
+            if constexpr (SLOT) { if (srow) ro += (long)min(max(srow[kbase + kr], 0), p.rows - 1) * p.tail_row; }
 #pragma unroll
             for (int s = 0; s < 4; ++s)
                 kf[u][s] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(kb + ro + 32 * s + 8 * g));
         }
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            const long ro = (long)min((lane >> 4) + 4 * i, nvalid - 1) * ldv;
+            const int kr = min((lane >> 4) + 4 * i, nvalid - 1);
+            long ro = (long)kr * ldv;
+            if constexpr (SLOT) { if (srow) ro += (long)min(max(srow[kbase + kr], 0), p.rows - 1) * p.tail_row; }
             vreg[i] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(vb + ro + (lane & 15) * 8));
         }
         // S^T, four key blocks of 16
@@ -236,6 +248,7 @@ int cogs_k_attention_decode(hipStream_t st, const CogsAttn& a, float* part_o, fl
     if ((long)((p.kend + 63) >> 6) * (a.nsplit + 1) > 0x7fffffffL) return COGS_E_INVALID;
     p.part_o = part_o; p.part_ml = part_ml;
     p.tail_k = p.tail_v = nullptr; p.ldq = p.tail_ld = p.tail_row = 0; p.rows = 1; p.ntile = 1; p.tail_len = 0;
+    p.tail_slot = nullptr; p.tail_slot_ld = 0;
     hipLaunchKernelGGL(attn_decode_kernel<false>, dim3(a.nsplit, a.hkv), dim3(256), 0, st, p);
     return COGS_LAUNCH_CHECK();
 }
@@ -256,6 +269,12 @@ int cogs_k_attention_decode_rows(hipStream_t st, const CogsAttnRows& a, float* p
     p.tail_k = (const bf16_t*)a.tail_k; p.tail_v = (const bf16_t*)a.tail_v;
     p.ldq = a.ldq; p.tail_ld = a.tail_ld; p.tail_row = a.tail_row;
     p.rows = a.rows; p.ntile = (a.rows * p.gsz + 15) / 16; p.tail_len = a.tail_len;
-    hipLaunchKernelGGL(attn_decode_kernel<true>, dim3(a.nsplit * p.ntile + a.rows, a.hkv), dim3(256), 0, st, p);
+    p.tail_slot = a.tail_slot; p.tail_slot_ld = a.tail_slot_ld;
+    if (a.tail_slot) {
+        if (a.tail_slot_ld < a.tail_len) return COGS_E_INVALID;
+        hipLaunchKernelGGL((attn_decode_kernel<true, true>), dim3(a.nsplit * p.ntile + a.rows, a.hkv), dim3(256), 0, st, p);
+    } else {
+        hipLaunchKernelGGL(attn_decode_kernel<true>, dim3(a.nsplit * p.ntile + a.rows, a.hkv), dim3(256), 0, st, p);
+    }
     return COGS_LAUNCH_CHECK();
 }

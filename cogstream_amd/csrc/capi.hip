@@ -207,6 +207,7 @@ cogs_status cogs_attention_rows(cogs_stream stream, const cogs_attn_rows_desc* d
     a.tail_k = d->tail_k; a.tail_v = d->tail_v; a.tail_ld = d->tail_ld; a.tail_row = d->tail_row_stride; a.tail_len = d->tail_len;
     a.O = d->O; a.rows = d->rows; a.hq = d->hq; a.hkv = d->hkv; a.head_dim = d->head_dim;
     a.nsplit = d->nsplit > 1 ? d->nsplit : 1; a.ws = d->ws; a.ws_bytes = d->ws_bytes;
+    a.tail_slot = d->tail_slot; a.tail_slot_ld = d->tail_slot_ld;
     return cogs_k_attention_rows((hipStream_t)stream, a);
 }
 
@@ -418,6 +419,18 @@ cogs_status cogs_topk(cogs_stream stream, const float* logits, int n, int top_k,
                       float* ws) {
     if (!ws) return COGS_E_WORKSPACE;
     return cogs_k_topk((hipStream_t)stream, logits, n, top_k, topk_val, topk_idx, ws);
+}
+
+cogs_status cogs_beam_topk_workspace_bytes(int rows, int n, int k, size_t* bytes) {
+    if (!bytes) return COGS_E_INVALID;
+    return cogs_k_beam_topk_ws(rows, n, k, bytes);
+}
+cogs_status cogs_beam_topk(cogs_stream stream, const float* scores, int rows, int n, int64_t ld, const float* row_add, int k,
+                           float* out_val, int32_t* out_row, int32_t* out_tok, void* ws, size_t ws_bytes) {
+    return cogs_k_beam_topk((hipStream_t)stream, scores, rows, n, ld, row_add, k, out_val, out_row, out_tok, ws, ws_bytes);
+}
+cogs_status cogs_sub_rows(cogs_stream stream, float* x, int rows, int n, int64_t ld, const float* sub) {
+    return cogs_k_sub_rows((hipStream_t)stream, x, rows, n, ld, sub);
 }
 
 }  // extern "C"

@@ -348,6 +348,13 @@ cogs_status cogs_lm_score(cogs_handle h, cogs_stream stream, const void* hidden,
 
 cogs_status cogs_llm_decode_rows(cogs_handle h, cogs_stream stream, const void* embeds, int R, cogs_kv_rows* kv, float* logits,
                                  void* ws, size_t ws_bytes) {
+    return cogs_llm_decode_rows_slots(h, stream, embeds, R, kv, nullptr, logits, ws, ws_bytes);
+}
+
+// tail_slot [R][tail_max] (null: row r reads slot r): row r's new K / V still goes to slot r, position tail_len -- the caller has
+// set tail_slot[r][tail_len] = r -- and the attention reads every row's tail through the table
+cogs_status cogs_llm_decode_rows_slots(cogs_handle h, cogs_stream stream, const void* embeds, int R, cogs_kv_rows* kv,
+                                       const int32_t* tail_slot, float* logits, void* ws, size_t ws_bytes) {
     if (!h || !h->llm_ok || !embeds || !kv || !logits || R <= 0) return COGS_E_INVALID;
     const cogs_llm_weights& w = h->llm;
     if (w.dtype != COGS_DT_BF16 || w.head_dim != 128 || R > 16) return COGS_E_UNSUPPORTED;
@@ -385,6 +392,7 @@ cogs_status cogs_llm_decode_rows(cogs_handle h, cogs_stream stream, const void* 
         a.tail_k = tk; a.tail_v = tv; a.tail_ld = kvd; a.tail_row = (long)tail_row; a.tail_len = tl + 1;
         a.O = b.att; a.rows = R; a.hq = w.heads; a.hkv = w.kv_heads; a.head_dim = hd;
         a.nsplit = nsplit; a.ws = b.split; a.ws_bytes = b.split_bytes;
+        a.tail_slot = tail_slot; a.tail_slot_ld = kv->tail_max;
         PROF(COGS_PROF_ATTN);
         return cogs_k_attention_rows(st, a);
     };

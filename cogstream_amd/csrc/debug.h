@@ -51,6 +51,7 @@
     X(vit_split_max, 1099511627776LL, "clips above this many patches are encoded on one stream")                           \
     X(llm_split_keys, 0, "> 0: keys per split of the decode attention (0: chosen from the context)")                        \
     X(llm_decode_fp8, 1, "cogs_llm_forward with e4m3 weights attached (cogs_llm_attach_fp8): 1 single-token steps read them, 0 the dequantised bf16 / fp32 copy (the in-process A/B)") \
+    X(beam_gather_tails, 0, "tests: 1 = beam search (llm.py, read through cogs_debug_get) copies every beam's tail behind its parent's per step and passes no slot table; 0 the tails stay where they were written and cogs_attention_rows reads them through the table") \
     X(km_row_groups, 0, "> 0: row groups of the k-means distance pass (0: sized to fill the chip)")                       \
     /* ---- teacher-forced scoring (csrc/lm_score.hip) ---- */                                                              \
     X(lm_score_rows, 2048, "cogs_lm_score / cogs_row_lse: rows of a logits panel")                                          \

@@ -95,6 +95,7 @@ struct CogsAttnRows {
     int rows = 0, hq = 1, hkv = 1, head_dim = 0;
     int nsplit = 1;                                              // splits of the shared keys (<= 127)
     void* ws = nullptr; size_t ws_bytes = 0;                     // (nsplit + 1) * rows * hq * (head_dim + 2) floats
+    const int32_t* tail_slot = nullptr; long tail_slot_ld = 0;   // non-null: row r's tail key j lives in tail slot tail_slot[r * ld + j]
 };
 int cogs_k_attention_decode_rows(hipStream_t st, const CogsAttnRows& a, float* part_o, float* part_ml);   // attn_decode.hip: partials
 int cogs_k_attention_combine(hipStream_t st, const float* part_o, const float* part_ml, int nparts, int heads, int head_dim,
@@ -180,6 +181,12 @@ size_t cogs_k_sample_ws();
 int cogs_k_sample(hipStream_t st, const float* logits, int n, float temperature, int top_k, double top_p, const float* draws, uint64_t seed,
                   uint64_t offset, int64_t* out_token, int32_t* kept_idx, float* kept_prob, int* n_kept, int kept_cap,
                   void* ws);
+
+// beam search (beam.hip): the k largest of scores[r][t] + row_add[r] over rows x n, descending, ties by ascending r * n + t
+int cogs_k_beam_topk_ws(int rows, int n, int k, size_t* bytes);
+int cogs_k_beam_topk(hipStream_t st, const float* scores, int rows, int n, long ld, const float* row_add, int k, float* out_val,
+                     int32_t* out_row, int32_t* out_tok, void* ws, size_t ws_bytes);
+int cogs_k_sub_rows(hipStream_t st, float* x, int rows, int n, long ld, const float* sub);   // x[r][:] -= sub[r]
 
 // teacher-forced scoring (lm_score.hip): a [rows, n] fp32 logits matrix is walked as rows_b x cols_p panels; every panel is
 // folded into 16 bytes of per-row state (maximum, sum of exp, first-maximum column); the last call writes the outputs

@@ -9,6 +9,7 @@ from typing import Dict, List, Optional, Sequence
 import torch
 
 from . import _lib as L
+from . import beam as beam_host
 from . import ops
 from .runtime import get_handle
 from .weights import LlmConfig, PackedLlm
@@ -17,12 +18,15 @@ from .weights import LlmConfig, PackedLlm
 MAX_RETURN_SEQUENCES = 16      # rows of one lockstep decode step: the 16 activation columns of the MFMA tile
 
 
-def check_num_return_sequences(n: int, do_sample: bool) -> int:
+def check_num_return_sequences(n: int, do_sample: bool, num_beams: int = 1) -> int:
     """the argument rules of generate(num_return_sequences=): transformers 4.46.3 refuses several greedy copies, the
-    lockstep step has 16 columns"""
+    lockstep step has 16 columns; with num_beams > 1 up to num_beams hypotheses may be returned (beam.check_beam_args)"""
     n = int(n)
     if n < 1 or n > MAX_RETURN_SEQUENCES:
         raise ValueError(f"num_return_sequences has to be between 1 and {MAX_RETURN_SEQUENCES}, but is {n}")
+    if int(num_beams) > 1:
+        beam_host.check_beam_args(num_beams, n, do_sample)
+        return n
     if n > 1 and not do_sample:
         raise ValueError(f"Greedy methods without beam search do not support `num_return_sequences` different than 1 (got {n}).")
     return n
@@ -267,7 +271,8 @@ class Qwen2Engine:
                  cache: Optional[KVCache] = None, ignore_eos: bool = False,
                  prefix: Optional[PrefixKV] = None, prefilled: Optional[dict] = None,
                  stage_times: Optional[dict] = None, num_return_sequences: int = 1,
-                 pad_token_id: Optional[int] = None):
+                 pad_token_id: Optional[int] = None, num_beams: int = 1, length_penalty: float = 1.0,
+                 early_stopping=False):
         """GenerationMixin.generate with inputs_embeds: prefill, then one cogs_llm_forward per token.
         Returns the NEW token ids only. Logits processors run in HF order:
         repetition penalty -> custom (allowed-id mask) -> temperature -> top-k -> top-p.
@@ -280,7 +285,16 @@ class Qwen2Engine:
         torch.multinomial does in the reference's CPU run, so the sampled ids are the reference's.
         num_return_sequences = N > 1 (sampling only, N <= 16): N continuations of the one prefilled prompt, advanced in
         lockstep by cogs_llm_decode_rows -> a list of N token lists (see _generate_rows); pad_token_id is accepted for
-        signature parity with GenerationMixin (the lists are ragged; CogReasoner.generate pads)."""
+        signature parity with GenerationMixin (the lists are ragged; CogReasoner.generate pads).
+        num_beams = B > 1 (2 .. 16, no sampling): beam search (see beam_search) -> the best hypothesis as a token list, or,
+        for num_return_sequences = N <= B, the N best as a list of lists."""
+        if int(num_beams) != 1:
+            seqs, _ = Qwen2Engine.beam_search(self, embeds, num_beams=num_beams, max_new_tokens=max_new_tokens, eos_token_id=eos_token_id,
+                                              num_return_sequences=num_return_sequences, length_penalty=length_penalty,
+                                              early_stopping=early_stopping, do_sample=do_sample,
+                                              repetition_penalty=repetition_penalty, allowed_ids=allowed_ids, prompt_ids=prompt_ids,
+                                              cache=cache, ignore_eos=ignore_eos, prefix=prefix, prefilled=prefilled)
+            return seqs[0] if int(num_return_sequences) == 1 else seqs
         if check_num_return_sequences(num_return_sequences, do_sample) > 1:
             return self._generate_rows(embeds, int(num_return_sequences), max_new_tokens=max_new_tokens, eos_token_id=eos_token_id,
                                        temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
@@ -343,8 +357,10 @@ class Qwen2Engine:
             cache.reset(min(cache.len, pos_start + stop_at - 1))
         return out
 
-    def decode_rows(self, embeds: torch.Tensor, kv: "L.KVRows") -> torch.Tensor:
-        """cogs_llm_decode_rows: one token per sequence, embeddings [R, H] -> fp32 logits [R, vocab]; advances kv.tail_len"""
+    def decode_rows(self, embeds: torch.Tensor, kv: "L.KVRows", tail_slot: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """cogs_llm_decode_rows: one token per sequence, embeddings [R, H] -> fp32 logits [R, vocab]; advances kv.tail_len.
+        tail_slot (cogs_llm_decode_rows_slots): int32 [R, kv.tail_max] on the device, row r reads tail position j from slot
+        tail_slot[r, j]; the caller has set tail_slot[r, kv.tail_len] = r"""
         self._activate()
         embeds = embeds.contiguous()
         R = embeds.shape[0]
@@ -353,18 +369,132 @@ class Qwen2Engine:
                 "cogs_llm_decode_rows_workspace_bytes")
         ws = self.handle.workspace("llm_rows", nbytes.value)
         logits = torch.empty(R, self.cfg.vocab_size, device=self.device, dtype=torch.float32)
+        if tail_slot is not None:
+            assert tail_slot.is_cuda and tail_slot.dtype == torch.int32 and tail_slot.shape == (R, kv.tail_max) and tail_slot.is_contiguous()
+            L.check(L.lib.cogs_llm_decode_rows_slots(self.handle.h, L.current_stream(), embeds.data_ptr(), R, C.byref(kv),
+                                                     tail_slot.data_ptr(), logits.data_ptr(), ws.data_ptr(), ws.numel()),
+                    "cogs_llm_decode_rows_slots")
+            return logits
         L.check(L.lib.cogs_llm_decode_rows(self.handle.h, L.current_stream(), embeds.data_ptr(), R, C.byref(kv), logits.data_ptr(),
                                            ws.data_ptr(), ws.numel()), "cogs_llm_decode_rows")
         return logits
 
-    def new_rows_kv(self, cache: KVCache, n_rows: int, tail_max: int):
+    def new_rows_kv(self, cache: KVCache, n_rows: int, tail_max: int, slots: bool = False):
         """the cogs_kv_rows view of `cache` (its first cache.len rows are the shared prompt) + fresh tails for n_rows
-        sequences; the tail tensors are returned too (they own the memory)"""
+        sequences; the tail tensors are returned too (they own the memory). slots: a fourth result, the int32 [n_rows,
+        tail_max] slot table of beam search (zeros: every entry names a valid slot)"""
         kvd = self.cfg.num_key_value_heads * self.cfg.head_dim
         tk = torch.empty(self.cfg.num_hidden_layers, n_rows, tail_max, kvd, device=self.device, dtype=self.dtype)
         tv = torch.empty_like(tk)
         kv = L.KVRows(cache.k.data_ptr(), cache.v.data_ptr(), cache.k.shape[1], cache.len, tk.data_ptr(), tv.data_ptr(), tail_max, 0)
+        if slots:
+            return kv, tk, tv, torch.zeros(n_rows, tail_max, device=self.device, dtype=torch.int32)
         return kv, tk, tv
+
+    def beam_search(self, embeds: torch.Tensor, *, num_beams: int, max_new_tokens: int, eos_token_id: Sequence[int] = (),
+                    num_return_sequences: int = 1, length_penalty: float = 1.0, early_stopping=False, do_sample: bool = False,
+                    repetition_penalty: float = 1.0, allowed_ids: Optional[Sequence[int]] = None,
+                    prompt_ids: Optional[torch.Tensor] = None, cache: Optional[KVCache] = None, ignore_eos: bool = False,
+                    prefix: Optional[PrefixKV] = None, prefilled: Optional[dict] = None, pad_token_id: Optional[int] = None,
+                    select_fn=None):
+        """GenerationMixin.generate(num_beams=B, do_sample=False) on one prefilled prompt -> (the num_return_sequences best
+        hypotheses as lists of new token ids, their length-penalised scores); the bookkeeping is beam.beam_search.
+        bf16 / head_dim 128: the B beams advance in lockstep (cogs_llm_decode_rows_slots). A beam's K / V rows stay in the tail
+        slot that wrote them; per step the int32 [B, t] slot table is reordered by the beams' parents (slot = slot[parents];
+        slot[:, t] = arange(B)) and the attention reads every tail through it -- nothing of the KV moves. The token histories of
+        the repetition penalty are reordered the same way. Then cogs_row_lse + cogs_sub_rows turn the step's logits into
+        log-probabilities in place, cogs_logits_process runs per row when a penalty or mask is on (HF applies its processors to the
+        log-probabilities in beam search), and cogs_beam_topk selects the candidates with row_add = the beam scores; the
+        candidates' (value, row, token) triples are the step's one read-back. The debug switch beam_gather_tails = 1 copies
+        the tails by parent instead and passes no table (tests: the two must agree bit for bit).
+        fp32 engines / head_dim != 128: the same loop over single-row steps, one private K / V copy per beam, gathered by
+        parent. The shared cache is left at the prompt length, so a PrefixKV stays valid. select_fn: ops.beam_topk."""
+        eos = [] if ignore_eos else sorted(set(int(e) for e in eos_token_id))
+        B = beam_host.check_beam_args(num_beams, num_return_sequences, do_sample, len(eos))
+        N = check_num_return_sequences(num_return_sequences, do_sample, B)
+        res, cache, _ = self._prefill(embeds, max_new_tokens, cache, prefix, prefilled)
+        P = cache.len
+        V = self.cfg.vocab_size
+        dev = self.device
+        allowed = (torch.tensor(list(allowed_ids), dtype=torch.int32, device=dev) if allowed_ids is not None else None)
+        n_prompt = int(prompt_ids.numel()) if prompt_ids is not None else 0
+        state = {"seen": torch.zeros(B, n_prompt + max(max_new_tokens, 1), dtype=torch.int64, device=dev), "t": 0}
+        if n_prompt:
+            state["seen"][:, :n_prompt] = prompt_ids.reshape(1, -1).to(dev)
+        need_proc = repetition_penalty != 1.0 or allowed is not None
+
+        def logprobs(logits):                       # fp32 [rows, V] logits -> log-probabilities, in place
+            return ops.sub_rows(logits, ops.row_lse(logits)["lse"])
+
+        def process(scores, t):
+            if need_proc:
+                for r in range(scores.shape[0]):
+                    prev = state["seen"][r, :n_prompt + t] if (n_prompt + t and repetition_penalty != 1.0) else None
+                    ops.logits_process(scores[r], prev, repetition_penalty, allowed, 1.0)
+            return scores
+
+        def advance(tokens, parents):               # the histories follow the beams; -> (tokens, parents) on the device, position
+            j = state["t"]
+            par = torch.tensor(parents, dtype=torch.int64, device=dev)
+            tok = torch.tensor(tokens, dtype=torch.int64, device=dev)
+            state["seen"] = state["seen"].index_select(0, par)
+            state["seen"][:, n_prompt + j] = tok
+            state["t"] = j + 1
+            return tok, par, j
+
+        lockstep = self.dtype == torch.bfloat16 and self.cfg.head_dim == 128
+        if lockstep:
+            kv, tail_k, tail_v, slot = self.new_rows_kv(cache, B, max(max_new_tokens, 1), slots=True)
+            gather = L.debug_get("beam_gather_tails") != 0
+            ident = torch.arange(B, dtype=torch.int32, device=dev)
+            tab = {"slot": slot}
+
+            def step(tokens, parents):
+                tok, par, j = advance(tokens, parents)
+                if gather:
+                    if j:
+                        tail_k[:, :, :j] = tail_k[:, par, :j]
+                        tail_v[:, :, :j] = tail_v[:, par, :j]
+                    table = None
+                else:
+                    table = tab["slot"].index_select(0, par)
+                    table[:, j] = ident
+                    tab["slot"] = table
+                return logprobs(self.decode_rows(self.embed_tokens(tok), kv, table))
+        else:
+            # per-beam private K / V rows [B][layers][max_new_tokens][kv_dim], replayed behind the prompt for each single-row step
+            # (the shape of _generate_rows's fallback) and gathered by parent
+            own = {"k": torch.empty((B, cache.k.shape[0], max(max_new_tokens, 1), cache.k.shape[2]), device=dev, dtype=self.dtype)}
+            own["v"] = torch.empty_like(own["k"])
+
+            def step(tokens, parents):
+                tok, par, j = advance(tokens, parents)
+                own["k"], own["v"] = own["k"].index_select(0, par), own["v"].index_select(0, par)
+                out = torch.empty(B, V, device=dev, dtype=torch.float32)
+                for r in range(B):
+                    cache.k[:, P:P + j] = own["k"][r, :, :j]
+                    cache.v[:, P:P + j] = own["v"][r, :, :j]
+                    cache.reset(P + j)
+                    out[r] = self.forward(self.embed_tokens(tok[r:r + 1]), cache)["logits"]
+                    own["k"][r, :, j] = cache.k[:, P + j]
+                    own["v"][r, :, j] = cache.v[:, P + j]
+                return logprobs(out)
+
+        def select(scores, row_add, k):             # the candidates come back in ONE copy: the step's synchronisation
+            val, crow, ctok = (select_fn or ops.beam_topk)(scores, row_add, k)
+            if val.is_cuda:
+                host = torch.stack([val.view(torch.int32), crow, ctok]).cpu()
+                val, crow, ctok = host[0].view(torch.float32), host[1], host[2]
+            return val, crow, ctok
+
+        try:
+            first = logprobs(res["logits"].view(1, V))
+            seqs, scores = beam_host.beam_search(step, select, first, num_beams=B, max_new_tokens=max_new_tokens,
+                                                 eos_token_id=eos, pad_token_id=pad_token_id, length_penalty=length_penalty,
+                                                 early_stopping=early_stopping, num_return_sequences=N, process_fn=process)
+        finally:
+            cache.reset(P)
+        return seqs, scores
 
     def _generate_rows(self, embeds, N, *, max_new_tokens, eos_token_id, temperature, top_k, top_p, repetition_penalty,
                        allowed_ids, prompt_ids, generator, sampler, seed, cache, ignore_eos, prefix, prefilled) -> List[List[int]]:

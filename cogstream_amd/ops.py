@@ -105,10 +105,11 @@ def gemm_rows(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = N
 
 def attention_rows(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, tail_k: torch.Tensor, tail_v: torch.Tensor, *,
                    prefix_len: int, tail_len: int, hq: int, hkv: int, head_dim: int = 128, nsplit: int = 1,
-                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   out: Optional[torch.Tensor] = None, tail_slot: Optional[torch.Tensor] = None) -> torch.Tensor:
     """cogs_attention_rows: q [rows, hq*hd] (pre-scaled; may be a column view), shared k / v [>= prefix_len, hkv*hd], tails
-    [rows, tail_max, hkv*hd] -> dense [rows, hq*hd]"""
-    _need_cuda(q, k, v, tail_k, tail_v, out)
+    [rows, tail_max, hkv*hd] -> dense [rows, hq*hd]. tail_slot int32 [rows, >= tail_len] (entries in [0, rows)): row r reads tail
+    key j from tail_k[tail_slot[r, j], j]"""
+    _need_cuda(q, k, v, tail_k, tail_v, out, tail_slot)
     rows = q.shape[0]
     assert tail_k.shape[0] == rows and tail_k.shape == tail_v.shape and tail_k.stride() == tail_v.stride()
     assert all(t.stride(-1) == 1 for t in (q, k, v, tail_k, tail_v)) and k.shape[0] >= prefix_len and tail_k.shape[1] >= tail_len
@@ -124,6 +125,9 @@ def attention_rows(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, tail_k: to
     d.O = ptr(out)
     d.rows, d.hq, d.hkv, d.head_dim = rows, hq, hkv, head_dim
     d.nsplit, d.ws, d.ws_bytes = nsplit, ptr(ws), ws.numel() * 4
+    if tail_slot is not None:
+        assert tail_slot.dtype == torch.int32 and tail_slot.dim() == 2 and tail_slot.shape[0] == rows and tail_slot.stride(1) == 1
+        d.tail_slot, d.tail_slot_ld = ptr(tail_slot), (tail_slot.stride(0) if rows > 1 else tail_slot.shape[1])
     check(L.lib.cogs_attention_rows(current_stream(), C.byref(d)), "cogs_attention_rows")
     return out
 
@@ -450,6 +454,53 @@ def topk(logits: torch.Tensor, k: int):
     ws = torch.empty(logits.numel(), device=logits.device, dtype=torch.float32)
     check(L.lib.cogs_topk(current_stream(), ptr(logits), logits.numel(), k, ptr(val), ptr(idx), ptr(ws)), "cogs_topk")
     return val, idx
+
+
+def beam_topk_cpu(scores: torch.Tensor, row_add: Optional[torch.Tensor], k: int):
+    """cogs_beam_topk's semantics in torch, for CPU tensors: v = scores + row_add[:, None] in fp32 (one addition; a sum of -0
+    counts as +0), the k largest in descending order, equal values by ascending flat index -- a stable sort on -v. -inf ranks
+    last, in index order. -> (values fp32 [k], rows int32 [k], tokens int32 [k])"""
+    rows, n = scores.shape
+    if not (1 <= k <= rows * n):
+        raise ValueError(f"k has to be between 1 and rows * n = {rows * n}, but is {k}")
+    v = scores.to(torch.float32)
+    v = (v + (row_add.to(torch.float32).reshape(rows, 1) if row_add is not None else 0.0)) + 0.0
+    flat = v.reshape(-1)
+    idx = torch.sort(-flat, stable=True).indices[:k]
+    return flat[idx].clone(), (idx // n).to(torch.int32), (idx % n).to(torch.int32)
+
+
+def beam_topk(scores: torch.Tensor, row_add: Optional[torch.Tensor], k: int):
+    """cogs_beam_topk: the k largest of scores[r, t] + row_add[r] over fp32 scores [rows, n] (unit column stride), descending,
+    equal values by ascending r * n + t -> (values fp32 [k], rows int32 [k], tokens int32 [k]) on the scores' device, no host
+    synchronisation. CPU scores take beam_topk_cpu (the host tests and anything that has its scores on the host)."""
+    assert scores.dim() == 2 and scores.dtype == torch.float32 and scores.stride(1) == 1
+    if not scores.is_cuda:
+        return beam_topk_cpu(scores, row_add, k)
+    rows, n = scores.shape
+    dev = scores.device
+    if row_add is not None:
+        row_add = row_add.to(dev, torch.float32, non_blocking=True).contiguous()
+        assert row_add.numel() == rows
+    out = torch.empty(3, k, device=dev, dtype=torch.int32)
+    val = out[0].view(torch.float32)
+    nbytes = C.c_size_t()
+    check(L.lib.cogs_beam_topk_workspace_bytes(rows, n, k, C.byref(nbytes)), "cogs_beam_topk_workspace_bytes")
+    ws = torch.empty(nbytes.value, device=dev, dtype=torch.uint8)
+    check(L.lib.cogs_beam_topk(current_stream(), ptr(scores), rows, n, scores.stride(0) if rows > 1 else max(n, scores.stride(0)),
+                               ptr(row_add), k, ptr(val), ptr(out[1]), ptr(out[2]), ptr(ws), ws.numel()), "cogs_beam_topk")
+    return val, out[1], out[2]
+
+
+def sub_rows(x: torch.Tensor, sub: torch.Tensor) -> torch.Tensor:
+    """cogs_sub_rows: x[r, :] -= sub[r] in place on fp32 [rows, n] (logits -> log-probabilities with sub = row_lse's lse)"""
+    _need_cuda(x, sub)
+    assert x.dim() == 2 and x.dtype == torch.float32 and x.stride(1) == 1 and sub.dtype == torch.float32 and sub.is_contiguous()
+    rows, n = x.shape
+    assert sub.numel() == rows
+    check(L.lib.cogs_sub_rows(current_stream(), ptr(x), rows, n, x.stride(0) if rows > 1 else max(n, x.stride(0)), ptr(sub)),
+          "cogs_sub_rows")
+    return x
 
 
 def sample(logits: torch.Tensor, top_k: int = 0, top_p: float = 1.0, draws: Optional[torch.Tensor] = None,

@@ -93,7 +93,8 @@ const char* cogs_debug_list(void);
  * "0.3" cogs_lm_score / cogs_row_lse, "0.4" cogs_gemv_fp8 / cogs_quantize_fp8_rows / cogs_llm_attach_fp8 (new entry points
  * only; every older signature and structure is unchanged). Added since without a new revision string (new entry points
  * and structures only): cogs_gemm_rows, cogs_attention_rows / cogs_attn_rows_desc, cogs_llm_decode_rows /
- * cogs_llm_decode_rows_workspace_bytes / cogs_kv_rows. */
+ * cogs_llm_decode_rows_workspace_bytes / cogs_kv_rows; cogs_attn_rows_desc.tail_slot / tail_slot_ld (appended, 0 = off),
+ * cogs_llm_decode_rows_slots, cogs_beam_topk / cogs_beam_topk_workspace_bytes, cogs_sub_rows. */
 
 /* C[M,N] = epilogue(A[M,K] . W[N,K]^T). nn.Linear / Conv2d(k=s=14) replacement
  * (model/modeling_videollama3_encoder.py:194-210,246-248,275,369-373; cogreasoner_chat.py:179-211).
@@ -256,7 +257,12 @@ cogs_status cogs_attention(cogs_stream stream, const cogs_attn_desc* d);
  * query columns are packed into MFMA tiles of 16; the shared keys are split over nsplit (1 .. 127) workgroups per tile, every
  * row's tail is one more partial, and one combine kernel merges the nsplit + 1 partials. O: dense [rows][hq * 128].
  * ws >= (nsplit + 1) * rows * hq * (head_dim + 2) * 4 bytes. COGS_E_UNSUPPORTED: dtype != COGS_DT_BF16, head_dim != 128,
- * hq / hkv > 16 or not integral, rows > 16. Zero-initialise the descriptor. */
+ * hq / hkv > 16 or not integral, rows > 16. Zero-initialise the descriptor.
+ * tail_slot (device int32, nullable): with a table, row r reads tail key j from tail_k / tail_v + tail_slot[r * tail_slot_ld + j] *
+ * tail_row_stride + j * tail_ld instead of from its own slot r -- beam search, where a row continues the keys another row wrote
+ * without copying them. Every entry the call reads (j < tail_len) must lie in [0, rows): the caller's contract, not checked on
+ * the device (an entry outside is clamped into the range, so a bad table reads wrong keys, not foreign memory).
+ * tail_slot_ld < tail_len returns COGS_E_INVALID. */
 typedef struct {
     int dtype;
     const void* Q; int64_t ldq;
@@ -265,6 +271,8 @@ typedef struct {
     void* O;
     int rows, hq, hkv, head_dim;
     int nsplit; void* ws; size_t ws_bytes;
+    const int32_t* tail_slot;
+    int64_t tail_slot_ld;
 } cogs_attn_rows_desc;
 cogs_status cogs_attention_rows(cogs_stream stream, const cogs_attn_rows_desc* d);
 
@@ -402,6 +410,20 @@ cogs_status cogs_row_lse_workspace_bytes(int rows, int n, size_t* bytes);
 cogs_status cogs_row_lse(cogs_stream stream, const float* logits, int rows, int n, int64_t ld, const int64_t* targets,
                          float* lse, float* target_logit, int64_t* argmax, float* max_logit, int32_t* n_bad, void* ws,
                          size_t ws_bytes);
+/* Beam search selection (GenerationMixin._beam_search: log_probs + running_beam_scores, then torch.topk over the flattened
+ * [num_beams * vocab] candidates): the k largest of v(r, t) = scores[r * ld + t] + row_add[r] (ONE fp32 addition; row_add
+ * device fp32 [rows], NULL = +0) over rows x n, written in descending order of v as out_val / out_row / out_tok [k] (device);
+ * equal values go by ascending flat index r * n + t. -inf scores are legal (the allowed-id mask) and rank last, in index order;
+ * a sum of -0 counts and is reported as +0. NaN is NOT supported (a NaN score may be dropped or ranked anywhere).
+ * 1 <= rows <= 16, 1 <= k <= 64, n <= 262144 (else COGS_E_UNSUPPORTED); k <= rows * n, n and ld multiples of 4, ld >= n, scores
+ * 16-byte aligned (else COGS_E_INVALID). Every score is read once, no floating-point atomics (the same call gives the same
+ * bits), no host synchronisation. ws >= cogs_beam_topk_workspace_bytes(rows, n, k). */
+cogs_status cogs_beam_topk_workspace_bytes(int rows, int n, int k, size_t* bytes);
+cogs_status cogs_beam_topk(cogs_stream stream, const float* scores, int rows, int n, int64_t ld, const float* row_add, int k,
+                           float* out_val, int32_t* out_row, int32_t* out_tok, void* ws, size_t ws_bytes);
+/* x[r * ld + i] -= sub[r] (fp32 [rows, n] in place; n and ld multiples of 4, x 16-byte aligned): logits -> log-probabilities
+ * with sub = the rows' lse of cogs_row_lse. */
+cogs_status cogs_sub_rows(cogs_stream stream, float* x, int rows, int n, int64_t ld, const float* sub);
 size_t cogs_sample_workspace_bytes(void);
 cogs_status cogs_sample(cogs_stream stream, const float* logits, int n, float temperature, int top_k, double top_p,
                         const float* draws,
@@ -552,6 +574,12 @@ cogs_status cogs_llm_decode_rows_workspace_bytes(cogs_handle h, int R, int max_p
  * cogs_llm_weights; cogs_debug_get("llm_last_decode_fp8") then reports 0. Row r's logits do not depend on the other rows. */
 cogs_status cogs_llm_decode_rows(cogs_handle h, cogs_stream stream, const void* embeds, int R, cogs_kv_rows* kv,
                                  float* logits, void* ws, size_t ws_bytes);
+/* The same step for beam search, where row r continues the sequence row parent[r] held one step ago: tail_slot (device int32
+ * [R][tail_max], row stride tail_max; NULL = cogs_llm_decode_rows) names, per row and tail position, the slot whose tail holds
+ * that position's K / V (cogs_attn_rows_desc.tail_slot). Row r's new K / V is still written at slot r, position tail_len: the
+ * caller sets tail_slot[r][tail_len] = r before the step. Nothing is copied; cogs_kv_rows is unchanged. */
+cogs_status cogs_llm_decode_rows_slots(cogs_handle h, cogs_stream stream, const void* embeds, int R, cogs_kv_rows* kv,
+                                       const int32_t* tail_slot, float* logits, void* ws, size_t ws_bytes);
 
 /* Teacher-forced scoring: the outputs of cogs_row_lse for logits = lm_head(hidden) WITHOUT the [S, vocab] logits --
  * Qwen2ForCausalLM.forward(labels=) / ForCausalLMLoss behind forward_train and forward (model/cogreasoner_chat.py:604-693,
