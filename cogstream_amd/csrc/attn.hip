@@ -1050,9 +1050,33 @@ __global__ __launch_bounds__(64) void attn_rowwise_kernel(AttnArgs p, int HD, in
 
 }  // namespace
 
+// the plan switches of debug.h, read once per call: another thread may set a switch mid-call (debug.h)
+AttnTuning cogs_k_attention_tuning() {
+    AttnTuning t;
+    t.attn_vit = g_cogs_debug.attn_vit; t.attn_vit_early = g_cogs_debug.attn_vit_early; t.attn_vit_len = g_cogs_debug.attn_vit_len;
+    t.attn_decode = g_cogs_debug.attn_decode; t.attn_combine32 = g_cogs_debug.attn_combine32;
+    t.attn_prefill_dma = g_cogs_debug.attn_prefill_dma; t.attn_prefill_deep = g_cogs_debug.attn_prefill_deep;
+    t.attn_prio = g_cogs_debug.attn_prio; t.attn_light_first = g_cogs_debug.attn_light_first; t.attn_nq = g_cogs_debug.attn_nq;
+    t.llm_split_keys = g_cogs_debug.llm_split_keys;
+    return t;
+}
+
+// validate -> snapshot -> plan (attn_plan.h: every routing condition, grid and workspace formula) -> launch the plan
 int cogs_k_attention(hipStream_t st, const CogsAttn& a) {
-    if (a.q_len <= 0 || a.hq <= 0 || a.hkv <= 0 || a.hq % a.hkv != 0) return COGS_E_INVALID;
-    if (a.head_dim > 256 || a.head_dim % 8 != 0) return COGS_E_UNSUPPORTED;
+    AttnQuery q;
+    q.bf16 = a.dtype == COGS_DT_BF16;
+    q.head_dim = a.head_dim; q.q_len = a.q_len; q.kv_len = a.kv_len; q.hq = a.hq; q.hkv = a.hkv;
+    q.ldq = a.ldq; q.ldk = a.ldk; q.ldv = a.ldv; q.ldo = a.ldo; q.head_stride = a.head_stride;
+    q.has_cu = a.cu_seqlens != nullptr; q.has_row_lo = a.row_lo != nullptr; q.has_ws = a.ws != nullptr;
+    q.nseg = a.nseg; q.max_seqlen = a.max_seqlen; q.uniform_seqlen = a.uniform_seqlen;
+    q.causal = a.causal; q.q_pos0 = a.q_pos0; q.q_prescaled = a.q_prescaled; q.force_rowwise = a.force_rowwise;
+    q.nsplit = a.nsplit; q.ws_bytes = a.ws_bytes;
+    const AttnPlan plan = cogs_plan_attention(q, cogs_k_attention_tuning());
+    if (plan.status != COGS_OK) return plan.status;
+    g_cogs_debug.attn_last_kernel = plan.kernel;
+    if (plan.vit_pipe) g_cogs_debug.attn_vit_last_end = plan.vit_end;
+    if (plan.kernel == 2 || plan.kernel == 3 || plan.kernel == 8) return cogs_k_attention_vit(st, a, plan);
+
     AttnArgs p;
     p.Q = a.Q; p.K = a.K; p.V = a.V; p.O = a.O;
     p.ldq = a.ldq; p.ldk = a.ldk; p.ldv = a.ldv; p.ldo = a.ldo;
@@ -1062,112 +1086,65 @@ int cogs_k_attention(hipStream_t st, const CogsAttn& a) {
     p.scale_log2 = a.q_prescaled ? 1.0f : a.scale * LOG2E;   // prescaled Q: scores are already in log2 units
     p.bias_log2 = a.bias * LOG2E;
     p.q_pos0 = a.q_pos0; p.causal = a.causal;
-    const int nseg = a.cu_seqlens ? a.nseg : 1;
-    p.nsplit = 1; p.gqa_pack = 0; p.q_prescaled = 0; p.part_o = nullptr; p.part_ml = nullptr;
-    const bool env_light_first = g_cogs_debug.attn_light_first == 1;   // A/B runs only
-    p.heavy_first = (a.causal && !a.cu_seqlens && a.q_len > 128 && !env_light_first) ? 1 : 0;
-    const int env_prio = (int)g_cogs_debug.attn_prio;   // in-run A/B at 15 395 tokens: 0 / 1 / 2 = 1.90-1.91 / 1.88-1.89 / 1.83 ms per layer
-    p.prio_mode = env_prio;
-    // the encoder's production shape (per-frame segments, hd 72, pre-scaled Q, no masks) has its own kernel
-    const bool env_old_vit = g_cogs_debug.attn_vit == 0;   // A/B runs only
-    if (a.dtype == COGS_DT_BF16 && !a.force_rowwise && a.head_dim == 72 && a.q_prescaled && a.cu_seqlens && !a.row_lo &&
-        !a.causal && a.nsplit <= 1 && a.hq == a.hkv && a.ldo % 8 == 0 && !env_old_vit)
-        return cogs_k_attention_vit(st, a);
-    if (a.head_stride > 0) return COGS_E_UNSUPPORTED;      // head-major Q / K / V: the encoder's production kernel only
-    if (a.dtype == COGS_DT_BF16 && !a.force_rowwise && (a.head_dim == 72 || a.head_dim == 128)) {
-        if (a.ldq % 8 || a.ldk % 8 || a.ldv % 8 || a.ldo % 4) return COGS_E_INVALID;
-        const int max_len = a.cu_seqlens ? a.max_seqlen : a.q_len;
-        int qtiles = (max_len + 127) / 128;
-        int gy = a.hq;
-        if (a.nsplit > 1) {
-            if (a.cu_seqlens || a.row_lo || a.nsplit > 128) return COGS_E_UNSUPPORTED;
-            const size_t need = (size_t)a.nsplit * a.q_len * a.hq * (a.head_dim + 2) * sizeof(float);
-            if (!a.ws || a.ws_bytes < need) return COGS_E_WORKSPACE;
-            p.nsplit = a.nsplit;
-            p.part_o = (float*)a.ws;
-            p.part_ml = p.part_o + (size_t)a.nsplit * a.q_len * a.hq * a.head_dim;
-        }
-        if (a.q_len == 1 && a.hq / a.hkv <= 16 && !a.cu_seqlens) { p.gqa_pack = 1; gy = a.hkv; }
-        dim3 grid(qtiles * p.nsplit, gy, nseg);
-        const int env_nq = (int)g_cogs_debug.attn_nq;
-        // 8 waves x 16 rows: measured faster for hd 128 (no spills, 4 waves per SIMD: causal prefill 2.58 -> 2.29 ms
-        // at 15k tokens), slower for hd 72 (0.49 -> 0.52 ms: its fragment reads make the LDS the busiest unit)
-        // (with pre-scaled Q the 4-wave hd 128 kernel needs 243 VGPRs and no longer spills: 2.34 -> 2.26 ms, so the
-        // light variant is only the default for the classic softmax)
-        const bool light = env_nq ? env_nq == 1 : (a.head_dim == 128 && !a.q_prescaled);
-        const bool pre = a.q_prescaled && !a.row_lo;
-        if (a.q_prescaled && a.row_lo) return COGS_E_UNSUPPORTED;   // the bias mode is parity-only and unscaled
-        p.q_prescaled = pre;
-#define COGS_ATTN_LAUNCH(HD_, NQ_, NT_)                                                                          \
-    do {                                                                                                         \
-        if (pre) hipLaunchKernelGGL((attn_fwd_bf16_kernel<HD_, NQ_, true>), grid, dim3(NT_), 0, st, p);          \
-        else hipLaunchKernelGGL((attn_fwd_bf16_kernel<HD_, NQ_, false>), grid, dim3(NT_), 0, st, p);             \
-    } while (0)
-        // the generated tokens' attention (one query row, key-split) has its own kernel: every wave owns whole tiles
-        const bool env_old_dec = g_cogs_debug.attn_decode == 0;   // A/B runs only
-        const bool env_no_dma = g_cogs_debug.attn_prefill_dma == 0;   // A/B runs only
-        // (every causal pre-scaled hd-128 call, whatever its length: a prompt continued behind a cached prefix with fewer than 128
-        // new rows must run the same per-row arithmetic as the full prompt -- PrefixKV's transparency, tests/test_gpu_models.py --
-        // and since round 5 this kernel's running maximum is no longer the general kernel's)
-        if (a.head_dim == 128 && pre && a.causal && p.nsplit == 1 && !p.gqa_pack && !a.row_lo && !env_no_dma && a.ldo % 8 == 0) {
-            // (two more forms were built, tested at full size and measured slower -- a ping-pong form, 1.89 vs 1.81-1.86 ms per layer
-            // at 15 395 tokens, and 64 query rows per wave, 2.94 vs 1.97 ms: tools/experiments/attn_prefill_variants.hip)
-            g_cogs_debug.attn_last_kernel = 5;
-            if (g_cogs_debug.attn_prefill_deep && p.prio_mode == 2) hipLaunchKernelGGL((attn_prefill_dma_kernel<1, 2>), grid, dim3(256), 0, st, p);
-            else if (g_cogs_debug.attn_prefill_deep) hipLaunchKernelGGL((attn_prefill_dma_kernel<1, -1>), grid, dim3(256), 0, st, p);
-            else hipLaunchKernelGGL((attn_prefill_dma_kernel<0, -1>), grid, dim3(256), 0, st, p);
-        } else if (a.head_dim == 128 && a.q_len == 1 && p.nsplit > 1 && p.gqa_pack && pre && !env_old_dec) {
-            const int rc = cogs_k_attention_decode(st, a, p.part_o, p.part_ml);
+    p.heavy_first = plan.heavy_first; p.prio_mode = plan.prio_mode;
+    p.nsplit = plan.nsplit; p.gqa_pack = plan.gqa_pack; p.q_prescaled = plan.q_prescaled;
+    p.part_o = plan.nsplit > 1 ? (float*)a.ws : nullptr;
+    p.part_ml = plan.nsplit > 1 ? p.part_o + plan.part_ml_off : nullptr;
+    const dim3 grid(plan.grid_x, plan.grid_y, plan.grid_z), block(plan.block_x);
+    switch (plan.kernel) {
+        case 5:
+            if (plan.deep && plan.prio_t == 2) hipLaunchKernelGGL((attn_prefill_dma_kernel<1, 2>), grid, block, 0, st, p);
+            else if (plan.deep) hipLaunchKernelGGL((attn_prefill_dma_kernel<1, -1>), grid, block, 0, st, p);
+            else hipLaunchKernelGGL((attn_prefill_dma_kernel<0, -1>), grid, block, 0, st, p);
+            break;
+        case 4: {
+            const int rc = cogs_k_attention_decode(st, a, plan, p.part_o, p.part_ml);
             if (rc != COGS_OK) return rc;
-            g_cogs_debug.attn_last_kernel = 4;
-        } else if (a.head_dim == 72) {
-            g_cogs_debug.attn_last_kernel = 1;
-            if (light && !p.gqa_pack) COGS_ATTN_LAUNCH(72, 1, 512);
-            else COGS_ATTN_LAUNCH(72, 2, 256);
-        } else {
-            g_cogs_debug.attn_last_kernel = 1;
-            if (light && !p.gqa_pack) COGS_ATTN_LAUNCH(128, 1, 512);
-            else COGS_ATTN_LAUNCH(128, 2, 256);
+            break;
         }
-#undef COGS_ATTN_LAUNCH
-        if (p.nsplit > 1) {
-            if (a.head_dim % 32 == 0 && g_cogs_debug.attn_combine32)
-                hipLaunchKernelGGL(attn_combine32_kernel, dim3(a.q_len, a.hq, a.head_dim / 32), dim3(256), 0, st, p.part_o, p.part_ml,
-                                   p.nsplit, a.q_len, a.hq, a.head_dim, (bf16_t*)a.O, a.ldo);
-            else
-                hipLaunchKernelGGL(attn_combine_kernel, dim3(a.q_len, a.hq), dim3(256), 0, st, p.part_o, p.part_ml, p.nsplit,
-                                   a.q_len, a.hq, a.head_dim, (bf16_t*)a.O, a.ldo);
-        }
-        return COGS_LAUNCH_CHECK();
+        case 1:
+#define COGS_ATTN_CASE(HD_, NQ_, PRE_) \
+    case HD_ * 100 + NQ_ * 10 + PRE_: hipLaunchKernelGGL((attn_fwd_bf16_kernel<HD_, NQ_, PRE_ != 0>), grid, block, 0, st, p); break
+            switch (plan.hd * 100 + plan.nq * 10 + plan.pre) {      // attn_fwd_bf16_kernel<hd, nq, pre>
+                COGS_ATTN_CASE(72, 1, 1);   COGS_ATTN_CASE(72, 1, 0);   COGS_ATTN_CASE(72, 2, 1);   COGS_ATTN_CASE(72, 2, 0);
+                COGS_ATTN_CASE(128, 1, 1);  COGS_ATTN_CASE(128, 1, 0);  COGS_ATTN_CASE(128, 2, 1);  COGS_ATTN_CASE(128, 2, 0);
+                default: return COGS_E_INVALID;      // no such instantiation: nothing is launched
+            }
+#undef COGS_ATTN_CASE
+            break;
+        case 7:
+            if (q.bf16) hipLaunchKernelGGL(attn_rowwise_kernel<bf16_t>, grid, block, 0, st, p, a.head_dim, plan.nseg);
+            else hipLaunchKernelGGL(attn_rowwise_kernel<float>, grid, block, 0, st, p, a.head_dim, plan.nseg);
+            break;
+        default: return COGS_E_INVALID;
     }
-    dim3 grid(a.q_len, a.hq);
-    g_cogs_debug.attn_last_kernel = 7;
-    if (a.dtype == COGS_DT_BF16)
-        hipLaunchKernelGGL(attn_rowwise_kernel<bf16_t>, grid, dim3(64), 0, st, p, a.head_dim, nseg);
-    else
-        hipLaunchKernelGGL(attn_rowwise_kernel<float>, grid, dim3(64), 0, st, p, a.head_dim, nseg);
+    if (plan.combine != ATTN_COMBINE_NONE)
+        return cogs_k_attention_combine(st, plan, p.part_o, p.part_ml, a.q_len, a.hq, a.head_dim, a.O, a.ldo);
     return COGS_LAUNCH_CHECK();
 }
 
-int cogs_k_attention_combine(hipStream_t st, const float* part_o, const float* part_ml, int nparts, int heads, int head_dim,
-                             void* O) {
-    if (nparts < 1 || nparts > 128 || heads < 1 || head_dim < 1 || head_dim > 256) return COGS_E_INVALID;
-    if (head_dim % 32 == 0 && g_cogs_debug.attn_combine32)
-        hipLaunchKernelGGL(attn_combine32_kernel, dim3(1, heads, head_dim / 32), dim3(256), 0, st, part_o, part_ml, nparts, 1, heads,
-                           head_dim, (bf16_t*)O, (long)heads * head_dim);
+// the plan's combine step: plan.parts partials of q_len x heads (row, head) slots -> bf16 O, rows ldo elements apart
+int cogs_k_attention_combine(hipStream_t st, const AttnPlan& plan, const float* part_o, const float* part_ml, int q_len, int heads,
+                             int head_dim, void* O, long ldo) {
+    const dim3 grid(plan.combine_x, plan.combine_y, plan.combine_z);
+    if (plan.combine == ATTN_COMBINE_SLICE32)
+        hipLaunchKernelGGL(attn_combine32_kernel, grid, dim3(256), 0, st, part_o, part_ml, plan.parts, q_len, heads, head_dim, (bf16_t*)O, ldo);
     else
-        hipLaunchKernelGGL(attn_combine_kernel, dim3(1, heads), dim3(256), 0, st, part_o, part_ml, nparts, 1, heads, head_dim,
-                           (bf16_t*)O, (long)heads * head_dim);
+        hipLaunchKernelGGL(attn_combine_kernel, grid, dim3(256), 0, st, part_o, part_ml, plan.parts, q_len, heads, head_dim, (bf16_t*)O, ldo);
     return COGS_LAUNCH_CHECK();
 }
 
+// multi-row decode step: the key-split partials (attn_decode.hip), then one combine over the rows * hq (row, head) slots
 int cogs_k_attention_rows(hipStream_t st, const CogsAttnRows& a) {
-    if (a.nsplit < 1 || a.nsplit > 127) return COGS_E_INVALID;
-    const size_t slots = (size_t)(a.nsplit + 1) * a.rows * a.hq;
-    if (!a.ws || a.ws_bytes < slots * (a.head_dim + 2) * sizeof(float)) return COGS_E_WORKSPACE;
+    AttnRowsQuery q;
+    q.rows = a.rows; q.hq = a.hq; q.hkv = a.hkv; q.head_dim = a.head_dim; q.prefix_len = a.prefix_len; q.tail_len = a.tail_len;
+    q.ldq = a.ldq; q.ldk = a.ldk; q.ldv = a.ldv; q.tail_ld = a.tail_ld; q.tail_row = a.tail_row; q.tail_slot_ld = a.tail_slot_ld;
+    q.has_slot = a.tail_slot != nullptr; q.has_ws = a.ws != nullptr; q.nsplit = a.nsplit; q.ws_bytes = a.ws_bytes;
+    const AttnPlan plan = cogs_plan_attention_rows(q, cogs_k_attention_tuning());
+    if (plan.status != COGS_OK) return plan.status;
     float* part_o = (float*)a.ws;
-    float* part_ml = part_o + slots * a.head_dim;
-    const int rc = cogs_k_attention_decode_rows(st, a, part_o, part_ml);
+    float* part_ml = part_o + plan.part_ml_off;
+    const int rc = cogs_k_attention_decode_rows(st, a, plan, part_o, part_ml);
     if (rc != COGS_OK) return rc;
-    return cogs_k_attention_combine(st, part_o, part_ml, a.nsplit + 1, a.rows * a.hq, a.head_dim, a.O);
+    return cogs_k_attention_combine(st, plan, part_o, part_ml, 1, a.rows * a.hq, a.head_dim, a.O, (long)a.rows * a.hq * a.head_dim);
 }

@@ -234,47 +234,37 @@ __global__ __launch_bounds__(256, 1) void attn_decode_kernel(DecodeAttnArgs p) {
 
 }  // namespace
 
-// single query row, bf16, hd 128, pre-scaled Q, keys split over nsplit workgroups per kv head; partials in the
-// layout attn.hip's attn_combine_kernel reads (q_len = 1)
-int cogs_k_attention_decode(hipStream_t st, const CogsAttn& a, float* part_o, float* part_ml) {
-    if (a.head_dim != 128 || a.q_len != 1 || a.nsplit < 1 || a.hq % a.hkv || a.hq / a.hkv > 16) return COGS_E_UNSUPPORTED;
-    if (a.ldk % 8 || a.ldv % 8) return COGS_E_INVALID;
+// single query row, bf16, hd 128, pre-scaled Q, keys split over plan.nsplit workgroups per kv head; partials in the
+// layout attn.hip's attn_combine_kernel reads (q_len = 1). Validation, key count and grid: cogs_plan_attention (attn_plan.h)
+int cogs_k_attention_decode(hipStream_t st, const CogsAttn& a, const AttnPlan& plan, float* part_o, float* part_ml) {
     DecodeAttnArgs p;
     p.Q = (const bf16_t*)a.Q; p.K = (const bf16_t*)a.K; p.V = (const bf16_t*)a.V;
     p.ldk = a.ldk; p.ldv = a.ldv;
-    p.kend = a.causal ? (a.q_pos0 + 1 < a.kv_len ? a.q_pos0 + 1 : a.kv_len) : a.kv_len;
-    if (p.kend < 1) return COGS_E_INVALID;
-    p.hq = a.hq; p.hkv = a.hkv; p.nsplit = a.nsplit; p.gsz = a.hq / a.hkv;
-    if ((long)((p.kend + 63) >> 6) * (a.nsplit + 1) > 0x7fffffffL) return COGS_E_INVALID;
+    p.kend = plan.kend;
+    p.hq = a.hq; p.hkv = a.hkv; p.nsplit = plan.nsplit; p.gsz = plan.gsz;
     p.part_o = part_o; p.part_ml = part_ml;
     p.tail_k = p.tail_v = nullptr; p.ldq = p.tail_ld = p.tail_row = 0; p.rows = 1; p.ntile = 1; p.tail_len = 0;
     p.tail_slot = nullptr; p.tail_slot_ld = 0;
-    hipLaunchKernelGGL(attn_decode_kernel<false>, dim3(a.nsplit, a.hkv), dim3(256), 0, st, p);
+    hipLaunchKernelGGL(attn_decode_kernel<false>, dim3(plan.grid_x, plan.grid_y), dim3(plan.block_x), 0, st, p);
     return COGS_LAUNCH_CHECK();
 }
 
 // `rows` query rows in lockstep over one shared prompt (cogs_attention_rows, include/cogs.h): key-split partials of the shared
-// keys + one partial per row for its own tail, part_o / part_ml sized for nsplit + 1 partials of rows * hq heads
-int cogs_k_attention_decode_rows(hipStream_t st, const CogsAttnRows& a, float* part_o, float* part_ml) {
-    if (a.head_dim != 128 || a.hkv < 1 || a.hq % a.hkv || a.hq / a.hkv > 16 || a.rows < 1 || a.rows > 16) return COGS_E_UNSUPPORTED;
-    if (a.nsplit < 1 || a.prefix_len < 1 || a.tail_len < 1) return COGS_E_INVALID;
-    if (a.ldk % 8 || a.ldv % 8 || a.ldq % 8 || a.tail_ld % 8 || a.tail_row % 8) return COGS_E_INVALID;
+// keys + one partial per row for its own tail, part_o / part_ml sized for plan.parts partials of rows * hq heads
+// (cogs_plan_attention_rows)
+int cogs_k_attention_decode_rows(hipStream_t st, const CogsAttnRows& a, const AttnPlan& plan, float* part_o, float* part_ml) {
     DecodeAttnArgs p;
     p.Q = (const bf16_t*)a.Q; p.K = (const bf16_t*)a.K; p.V = (const bf16_t*)a.V;
     p.ldk = a.ldk; p.ldv = a.ldv;
-    p.kend = a.prefix_len;
-    p.hq = a.hq; p.hkv = a.hkv; p.nsplit = a.nsplit; p.gsz = a.hq / a.hkv;
-    if ((long)((p.kend + 63) >> 6) * (a.nsplit + 1) > 0x7fffffffL) return COGS_E_INVALID;
+    p.kend = plan.kend;
+    p.hq = a.hq; p.hkv = a.hkv; p.nsplit = plan.nsplit; p.gsz = plan.gsz;
     p.part_o = part_o; p.part_ml = part_ml;
     p.tail_k = (const bf16_t*)a.tail_k; p.tail_v = (const bf16_t*)a.tail_v;
     p.ldq = a.ldq; p.tail_ld = a.tail_ld; p.tail_row = a.tail_row;
-    p.rows = a.rows; p.ntile = (a.rows * p.gsz + 15) / 16; p.tail_len = a.tail_len;
+    p.rows = a.rows; p.ntile = plan.ntile; p.tail_len = a.tail_len;
     p.tail_slot = a.tail_slot; p.tail_slot_ld = a.tail_slot_ld;
-    if (a.tail_slot) {
-        if (a.tail_slot_ld < a.tail_len) return COGS_E_INVALID;
-        hipLaunchKernelGGL((attn_decode_kernel<true, true>), dim3(a.nsplit * p.ntile + a.rows, a.hkv), dim3(256), 0, st, p);
-    } else {
-        hipLaunchKernelGGL(attn_decode_kernel<true>, dim3(a.nsplit * p.ntile + a.rows, a.hkv), dim3(256), 0, st, p);
-    }
+    const dim3 grid(plan.grid_x, plan.grid_y), block(plan.block_x);
+    if (plan.rows_slot) hipLaunchKernelGGL((attn_decode_kernel<true, true>), grid, block, 0, st, p);
+    else hipLaunchKernelGGL(attn_decode_kernel<true>, grid, block, 0, st, p);
     return COGS_LAUNCH_CHECK();
 }

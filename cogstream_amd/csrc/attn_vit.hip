@@ -25,7 +25,6 @@
 //     four different 64-B bank quarters for the transposing read). 46 KiB per workgroup: 3 workgroups per CU.
 #include "common.h"
 #include "kernels.h"
-#include "debug.h"
 #include <stdlib.h>
 
 namespace {
@@ -783,34 +782,23 @@ __global__ __launch_bounds__(256, 2) void attn_vit_pipe_kernel(VitAttnArgs p) {
 
 }  // namespace
 
-// block-diagonal bf16 attention with pre-scaled Q, hd 72, hq == hkv
-int cogs_k_attention_vit(hipStream_t st, const CogsAttn& a) {
-    if (a.head_dim != 72 || !a.cu_seqlens || a.nseg <= 0 || a.hq != a.hkv) return COGS_E_UNSUPPORTED;
-    if (a.ldq % 8 || a.ldk % 8 || a.ldv % 8 || a.ldo % 8) return COGS_E_INVALID;
+// block-diagonal bf16 attention with pre-scaled Q, hd 72, hq == hkv: launches what cogs_plan_attention (attn_plan.h) chose --
+// kernel 2 unpipelined, 3 / 8 pipelined on token- / head-major Q / K / V with the ragged end (vit_r, vit_nlb)
+int cogs_k_attention_vit(hipStream_t st, const CogsAttn& a, const AttnPlan& plan) {
     VitAttnArgs p;
     p.Q = (const bf16_t*)a.Q; p.K = (const bf16_t*)a.K; p.V = (const bf16_t*)a.V; p.O = (bf16_t*)a.O;
     p.ldq = a.ldq; p.ldk = a.ldk; p.ldv = a.ldv; p.ldo = a.ldo;
     p.cu = a.cu_seqlens;
-    p.nseg = a.nseg; p.heads = a.hq; p.nqb = (a.max_seqlen + 127) / 128;
-    p.head_stride = a.head_stride > 0 ? a.head_stride : 72;
-    if (a.head_stride > 0 && (a.ldq != 72 || a.ldk != 72 || a.ldv != 72)) return COGS_E_INVALID;
-    p.uniform_len = (a.uniform_seqlen > 0 && (long)a.uniform_seqlen * a.nseg == a.q_len && a.uniform_seqlen == a.max_seqlen) ? a.uniform_seqlen : 0;
-    if (p.nseg > 65535 || p.heads > 65535 || (long)p.nqb * 8 > 0x7fffffffL) return COGS_E_INVALID;
-    p.xcd_order = p.heads % 8 == 0;
-    const dim3 grid = p.xcd_order ? dim3(p.nqb * 8, p.heads / 8, p.nseg) : dim3(p.nqb, p.heads, p.nseg);
-    const int variant = (int)g_cogs_debug.attn_vit;     // 1: unpipelined (A/B runs)
-    const int env_early = (int)g_cogs_debug.attn_vit_early;
-    p.early_prefetch = env_early;
-    if (variant == 1 || a.ldk != a.ldv) { g_cogs_debug.attn_last_kernel = 2; hipLaunchKernelGGL(attn_vit_kernel<72>, grid, dim3(256), 0, st, p); }
+    p.nseg = a.nseg; p.heads = a.hq; p.nqb = plan.nqb;
+    p.head_stride = plan.head_stride;
+    p.uniform_len = plan.uniform_len;
+    p.xcd_order = plan.xcd_order;
+    p.early_prefetch = plan.early_prefetch;
+    const dim3 grid(plan.grid_x, plan.grid_y, plan.grid_z), block(plan.block_x);
+    if (!plan.vit_pipe) hipLaunchKernelGGL(attn_vit_kernel<72>, grid, block, 0, st, p);
     else {
-        g_cogs_debug.attn_last_kernel = a.head_stride > 0 ? 8 : 3;
-        // one video (all segments alike, 4 tiles or more): the instantiation whose ragged end has this length's shape
-        const int nt = (p.uniform_len + 63) >> 6;
-        const int r = (g_cogs_debug.attn_vit_len != 0 && p.uniform_len > 0 && nt >= 4) ? 4 + ((nt - 4) & 3) : 0;
-        const int nlb = p.uniform_len - 64 * (nt - 1) > 32 ? 2 : 1;
-#define COGS_AV_LAUNCH(R_, B_) hipLaunchKernelGGL((attn_vit_pipe_kernel<72, R_, B_>), grid, dim3(256), 0, st, p)
-        g_cogs_debug.attn_vit_last_end = r * 10 + (r ? nlb : 0);
-        switch (r * 10 + (r ? nlb : 0)) {
+#define COGS_AV_LAUNCH(R_, B_) hipLaunchKernelGGL((attn_vit_pipe_kernel<72, R_, B_>), grid, block, 0, st, p)
+        switch (plan.vit_r * 10 + plan.vit_nlb) {
             case 41: COGS_AV_LAUNCH(4, 1); break;   case 42: COGS_AV_LAUNCH(4, 2); break;
             case 51: COGS_AV_LAUNCH(5, 1); break;   case 52: COGS_AV_LAUNCH(5, 2); break;
             case 61: COGS_AV_LAUNCH(6, 1); break;   case 62: COGS_AV_LAUNCH(6, 2); break;

@@ -2,29 +2,6 @@
 // multi-row decode step and teacher-forced scoring. Handle, carver and profiling bracket: capi_internal.h.
 #include "capi_internal.h"
 
-static int llm_nsplit(int ctx) {
-    // decode attention: the keys are split over workgroups (x kv heads) and combined by a second kernel
-    // measured (ms/token, 7B, kv heads 4): context 15 360: 256 keys per split 3.62, 128: 3.67, 64: 3.66, 512: 3.72;
-    // context 2 048: 256: 3.51, 128: 3.42, 64: 3.39 -- i.e. at least ~32 splits, of 64..256 keys
-    // => at least 32 splits while a split keeps 64 keys, 256 keys per split beyond that (monotonic in ctx: the
-    // workspace is sized with the largest context)
-    const int env_keys = (int)g_cogs_debug.llm_split_keys;
-    int n;
-    if (env_keys > 0) n = (ctx + env_keys - 1) / env_keys;
-    else {
-        n = (ctx + 255) / 256;
-        if (n < 32) n = 32;
-        const int cap = (ctx + 63) / 64;
-        if (n > cap) n = cap;
-    }
-    if (n < 1) n = 1;
-    if (n > 128) n = 128;
-    return n;
-}
-
-// the single-row split rule; the rows' tails are one more partial (<= 128 in all)
-static int rows_nsplit(int prefix_len) { return llm_nsplit(prefix_len) > 127 ? 127 : llm_nsplit(prefix_len); }
-
 // workspace of a forward over S rows, or of a lockstep step over R rows (base == nullptr: only `bytes` is meaningful)
 struct LlmScratch {
     void *x, *ln, *qkv, *att, *act;      // residual stream, RMSNorm(x), [q | k | v], attention output, MLP hidden
@@ -43,23 +20,24 @@ static void llm_scratch_rows(const cogs_llm_weights& w, int M, Carver& c, LlmScr
     s.act = c.take((size_t)M * w.inter * es);
     s.rc = (float*)c.take((size_t)M * (w.head_dim / 2) * 2 * sizeof(float));
 }
-static LlmScratch llm_scratch(const cogs_llm_weights& w, int S, int max_ctx, void* base) {
+// (split counts and partial-buffer sizes: attn_plan.h, under the switches `t` the caller snapshot once)
+static LlmScratch llm_scratch(const cogs_llm_weights& w, int S, int max_ctx, const AttnTuning& t, void* base) {
     Carver c(base);
     LlmScratch s{};
     llm_scratch_rows(w, S, c, s);
-    s.split_bytes = (size_t)llm_nsplit(max_ctx) * w.heads * (w.head_dim + 2) * sizeof(float);
+    s.split_bytes = cogs_attn_split_ws_bytes(cogs_attn_nsplit(max_ctx, t), 1, w.heads, w.head_dim);
     s.split = c.take(s.split_bytes);
     s.pos = (int32_t*)c.take((size_t)S * sizeof(int32_t));          // per-row positions (segmented forward)
     s.cu = (int32_t*)c.take(((size_t)S + 1) * sizeof(int32_t));     // cu_seqlens (at most S segments)
     s.bytes = c.off;
     return s;
 }
-static LlmScratch rows_scratch(const cogs_llm_weights& w, int R, int max_prefix, void* base) {
+static LlmScratch rows_scratch(const cogs_llm_weights& w, int R, int max_prefix, const AttnTuning& t, void* base) {
     Carver c(base);
     LlmScratch s{};
     llm_scratch_rows(w, R, c, s);
     s.pos = (int32_t*)c.take((size_t)R * sizeof(int32_t));
-    s.split_bytes = (size_t)(rows_nsplit(max_prefix) + 1) * R * w.heads * (w.head_dim + 2) * sizeof(float);
+    s.split_bytes = cogs_attn_split_ws_bytes(cogs_attn_rows_nsplit(max_prefix, t) + 1, R, w.heads, w.head_dim);
     s.split = c.take(s.split_bytes);
     s.bytes = c.off;
     return s;
@@ -147,7 +125,8 @@ static cogs_status llm_forward_impl(cogs_handle h, cogs_stream stream, const voi
     const int pos0 = kv ? kv->len : 0;
     const int ctx = pos0 + S;
     if (kv && (!kv->k || !kv->v || ctx > kv->max_len)) return COGS_E_INVALID;
-    const LlmScratch b = llm_scratch(w, S, ctx, ws);
+    const AttnTuning tune = cogs_k_attention_tuning();
+    const LlmScratch b = llm_scratch(w, S, ctx, tune, ws);
     if (!ws || ws_bytes < b.bytes) return COGS_E_WORKSPACE;
     int max_seg = 0;
     if (nseg > 0) {
@@ -198,7 +177,7 @@ static cogs_status llm_forward_impl(cogs_handle h, cogs_stream stream, const voi
         a.q_len = S; a.kv_len = ctx; a.hq = w.heads; a.hkv = w.kv_heads; a.head_dim = hd; a.scale = 1.0f / sqrtf((float)hd);
         a.causal = 1; a.q_pos0 = pos0; a.q_prescaled = prescale_q;
         if (nseg > 0) { a.cu_seqlens = b.cu; a.nseg = nseg; a.max_seqlen = max_seg; }
-        if (S == 1 && dt == COGS_DT_BF16 && hd == 128) { a.nsplit = llm_nsplit(ctx); a.ws = b.split; a.ws_bytes = b.split_bytes; }
+        if (S == 1 && dt == COGS_DT_BF16 && hd == 128) { a.nsplit = cogs_attn_nsplit(ctx, tune); a.ws = b.split; a.ws_bytes = b.split_bytes; }
         PROF(COGS_PROF_ATTN);
         return cogs_k_attention(st, a);
     };
@@ -283,13 +262,13 @@ cogs_status cogs_llm_attach_fp8(cogs_handle h, const cogs_llm_fp8_weights* w) {
 
 cogs_status cogs_llm_workspace_bytes(cogs_handle h, int max_tokens, int max_context, size_t* bytes) {
     if (!h || !h->llm_ok || !bytes || max_tokens <= 0) return COGS_E_INVALID;
-    *bytes = llm_scratch(h->llm, max_tokens, max_context, nullptr).bytes;
+    *bytes = llm_scratch(h->llm, max_tokens, max_context, cogs_k_attention_tuning(), nullptr).bytes;
     return COGS_OK;
 }
 
 cogs_status cogs_llm_decode_rows_workspace_bytes(cogs_handle h, int R, int max_prefix, size_t* bytes) {
     if (!h || !h->llm_ok || !bytes || R <= 0 || max_prefix <= 0) return COGS_E_INVALID;
-    *bytes = rows_scratch(h->llm, R, max_prefix, nullptr).bytes;
+    *bytes = rows_scratch(h->llm, R, max_prefix, cogs_k_attention_tuning(), nullptr).bytes;
     return COGS_OK;
 }
 
@@ -365,7 +344,8 @@ cogs_status cogs_llm_decode_rows_slots(cogs_handle h, cogs_stream stream, const 
     const int dt = w.dtype;
     const size_t es = esize(dt);
     const int H = w.hidden, hd = w.head_dim, kvd = w.kv_heads * hd, qd_q = w.heads * hd, qd = qd_q + 2 * kvd;
-    const LlmScratch b = rows_scratch(w, R, kv->prefix_len, ws);
+    const AttnTuning tune = cogs_k_attention_tuning();
+    const LlmScratch b = rows_scratch(w, R, kv->prefix_len, tune, ws);
     if (!ws || ws_bytes < b.bytes) return COGS_E_WORKSPACE;
     // the e4m3 codes serve single-row steps only: this step reads the (dequantised) matrices of cogs_llm_weights
     g_cogs_debug.llm_last_decode_fp8 = 0;
@@ -373,7 +353,7 @@ cogs_status cogs_llm_decode_rows_slots(cogs_handle h, cogs_stream stream, const 
     if (hipMemcpyAsync(b.x, embeds, (size_t)R * H * es, hipMemcpyDeviceToDevice, st) != hipSuccess) return COGS_E_HIP;
     if (hipMemsetD32Async((hipDeviceptr_t)b.pos, position, R, st) != hipSuccess) return COGS_E_HIP;
     { PROF(COGS_PROF_OTHER); COGS_TRY(cogs_k_llm_rope_table(st, b.rc, nullptr, b.pos, 0, R, h->llm_inv_freq, hd / 2)); }
-    const int nsplit = rows_nsplit(kv->prefix_len);
+    const int nsplit = cogs_attn_rows_nsplit(kv->prefix_len, tune);
     const size_t tail_row = (size_t)kv->tail_max * kvd;               // elements between two rows' tails
     auto linear = [&](CogsGemm& g, const uint8_t*, const float*) -> int { return cogs_k_gemm_rows(st, g); };
     // K / V: every row's new K / V goes behind its own tail; the attention reads the shared prefix and the row's tail

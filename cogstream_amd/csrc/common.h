@@ -188,12 +188,7 @@ __device__ __forceinline__ float silu_f(float x) {
     return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x));
 }
 
-// status codes shared with include/cogs.h
-#define COGS_OK 0
-#define COGS_E_INVALID (-1)
-#define COGS_E_HIP (-2)
-#define COGS_E_UNSUPPORTED (-3)
-#define COGS_E_WORKSPACE (-4)
+#include "status.h"      // status codes shared with include/cogs.h
 
 #define COGS_DT_BF16 0
 #define COGS_DT_F32 1

@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "attn_plan.h"
 
 #define COGS_ACT_NONE 0
 #define COGS_ACT_GELU_TANH 1
@@ -76,14 +77,17 @@ struct CogsAttn {
     int q_pos0 = 0;
     int force_rowwise = 0;
     int nsplit = 1;                   // >1: split the keys over blocks (decode); needs ws
-    void* ws = nullptr;               // nsplit*q_len*hq*(head_dim+2) floats
+    void* ws = nullptr;               // cogs_attn_split_ws_bytes(nsplit, q_len, hq, head_dim) (attn_plan.h)
     size_t ws_bytes = 0;
     int q_prescaled = 0;              // Q already multiplied by scale*log2(e) (bf16 MFMA kernels only; no bias mode)
     int uniform_seqlen = 0;           // internal hint: > 0 = every cu_seqlens segment has exactly this many rows, in order
     long head_stride = 0;             // > 0: head-major Q / K / V (include/cogs.h cogs_attn_desc.head_stride); ViT kernel only
 };
-int cogs_k_attention_vit(hipStream_t st, const struct CogsAttn& a);   // attn_vit.hip: block-diagonal, hd 72, pre-scaled Q
-int cogs_k_attention_decode(hipStream_t st, const struct CogsAttn& a, float* part_o, float* part_ml);   // attn_decode.hip: one query row, hd 128, key-split partials
+// cogs_k_attention / cogs_k_attention_rows snapshot the plan switches once (cogs_k_attention_tuning), take the plan of attn_plan.h and
+// launch it; the launchers that take an AttnPlan are their halves in the other kernel files and launch what that plan says
+AttnTuning cogs_k_attention_tuning();     // attn.hip: the plan switches of debug.h as they are now
+int cogs_k_attention_vit(hipStream_t st, const struct CogsAttn& a, const AttnPlan& plan);   // attn_vit.hip: block-diagonal, hd 72, pre-scaled Q
+int cogs_k_attention_decode(hipStream_t st, const struct CogsAttn& a, const AttnPlan& plan, float* part_o, float* part_ml);   // attn_decode.hip: one query row, hd 128, key-split partials
 int cogs_k_attention(hipStream_t st, const CogsAttn& a);
 // lockstep decode of `rows` sequences over one prompt (include/cogs.h cogs_attn_rows_desc): bf16, hd 128, pre-scaled Q
 struct CogsAttnRows {
@@ -94,12 +98,12 @@ struct CogsAttnRows {
     void* O = nullptr;                                           // dense [rows][hq * 128]
     int rows = 0, hq = 1, hkv = 1, head_dim = 0;
     int nsplit = 1;                                              // splits of the shared keys (<= 127)
-    void* ws = nullptr; size_t ws_bytes = 0;                     // (nsplit + 1) * rows * hq * (head_dim + 2) floats
+    void* ws = nullptr; size_t ws_bytes = 0;                     // cogs_attn_split_ws_bytes(nsplit + 1, rows, hq, head_dim) (attn_plan.h)
     const int32_t* tail_slot = nullptr; long tail_slot_ld = 0;   // non-null: row r's tail key j lives in tail slot tail_slot[r * ld + j]
 };
-int cogs_k_attention_decode_rows(hipStream_t st, const CogsAttnRows& a, float* part_o, float* part_ml);   // attn_decode.hip: partials
-int cogs_k_attention_combine(hipStream_t st, const float* part_o, const float* part_ml, int nparts, int heads, int head_dim,
-                             void* O);   // attn.hip: nparts <= 128 partials of `heads` (row, head) slots -> dense bf16 O [heads][head_dim]
+int cogs_k_attention_decode_rows(hipStream_t st, const CogsAttnRows& a, const AttnPlan& plan, float* part_o, float* part_ml);   // attn_decode.hip: partials
+int cogs_k_attention_combine(hipStream_t st, const AttnPlan& plan, const float* part_o, const float* part_ml, int q_len, int heads,
+                             int head_dim, void* O, long ldo);   // attn.hip: plan.parts <= 128 partials of q_len x heads slots -> bf16 O
 int cogs_k_attention_rows(hipStream_t st, const CogsAttnRows& a);     // both of the above
 // gemm_rows.hip: bf16, 1 <= M <= 16, weights streamed once as the MFMA operand (not reachable through cogs_k_gemm: its plan is pinned)
 int cogs_k_gemm_rows(hipStream_t st, const CogsGemm& g);

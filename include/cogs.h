@@ -225,7 +225,8 @@ cogs_status cogs_quantize_fp8_rows(cogs_stream stream, int dtype, const void* w,
  * row_lo/row_hi (device int32 [q_len], nullable): eager-reference mode, every query sees all
  * keys and `bias` is added to the logits of keys in [row_lo[q], row_hi[q]) (:257-266).
  * causal: key j visible to query i iff j <= i + q_pos0 (Qwen2; q_pos0 = kv_len - q_len).
- * nsplit > 1 splits the keys over workgroups (decode); ws >= nsplit*q_len*hq*(head_dim+2)*4 bytes.
+ * nsplit > 1 splits the keys over workgroups (decode); ws >= nsplit*q_len*hq*(head_dim+2)*4 bytes (the library computes this
+ * in one place: csrc/attn_plan.h, cogs_attn_split_ws_bytes; which kernel a descriptor gets: cogs_plan_attention there).
  * O: only rows [0, q_len) x columns [0, hq*head_dim) are written; the columns up to ldo and everything before and after
  * keep their bits. Keys past kv_len / past the last segment and Q rows past q_len are never given weight. */
 typedef struct {
@@ -256,7 +257,7 @@ cogs_status cogs_attention(cogs_stream stream, const cogs_attn_desc* d);
  * stride tail_ld; all strides in elements, multiples of 8). prefix_len >= 1, tail_len >= 1. Per kv head the rows * (hq / hkv)
  * query columns are packed into MFMA tiles of 16; the shared keys are split over nsplit (1 .. 127) workgroups per tile, every
  * row's tail is one more partial, and one combine kernel merges the nsplit + 1 partials. O: dense [rows][hq * 128].
- * ws >= (nsplit + 1) * rows * hq * (head_dim + 2) * 4 bytes. COGS_E_UNSUPPORTED: dtype != COGS_DT_BF16, head_dim != 128,
+ * ws >= (nsplit + 1) * rows * hq * (head_dim + 2) * 4 bytes (cogs_attn_split_ws_bytes with nsplit + 1 parts). COGS_E_UNSUPPORTED: dtype != COGS_DT_BF16, head_dim != 128,
  * hq / hkv > 16 or not integral, rows > 16. Zero-initialise the descriptor.
  * tail_slot (device int32, nullable): with a table, row r reads tail key j from tail_k / tail_v + tail_slot[r * tail_slot_ld + j] *
  * tail_row_stride + j * tail_ld instead of from its own slot r -- beam search, where a row continues the keys another row wrote

@@ -176,7 +176,7 @@ BIG = 3.0e4          # large finite filler: a key read from the wrong row or pas
 
 
 def _nsplit(ctx):
-    """csrc/capi_llm.hip::llm_nsplit (at most 127 here: the tails are one more partial)"""
+    """csrc/attn_plan.h::cogs_attn_nsplit (at most 127 here: the tails are one more partial)"""
     return min(max(min(max((ctx + 255) // 256, 32), (ctx + 63) // 64), 1), 127)
 
 

@@ -1,8 +1,8 @@
 // Stand-alone timing harness for csrc/attn_vit.hip (ViT block-diagonal attention, hd 72):
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -I cogstream_amd/csrc tools/micro/attn_vit_micro.cpp -o tools/micro/attn_vit_micro
-//   attn_vit_micro [frames] [rows per frame] [layout: 0 token-major fused qkv, 1 head-major q | k | v]
+//   attn_vit_micro [frames] [rows per frame] [layout: 0 token-major fused qkv, 1 head-major q | k | v] [attn_vit_len: 0 run-time end]
+// The launch is the one cogs_plan_attention_vit (csrc/attn_plan.h) gives for the descriptor, as cogs_k_attention would take it.
 #include "../../cogstream_amd/csrc/attn_vit.hip"
-CogsDebug g_cogs_debug;
 #include <cstdio>
 #include <cstring>
 #include <cmath>
@@ -40,13 +40,21 @@ int main(int argc, char** argv) {
         a.K = qkv + L * H; a.V = qkv + 2 * L * H; a.ldq = a.ldk = a.ldv = hd; a.head_stride = L * hd;
     }
     a.q_len = a.kv_len = (int)L; a.hq = a.hkv = heads; a.head_dim = hd; a.q_prescaled = 1;
-    if (argc > 4) g_cogs_debug.attn_vit_len = atoi(argv[4]);      // 0: the run-time-length kernel for every frame size
+    AttnTuning tuning;
+    if (argc > 4) tuning.attn_vit_len = atoi(argv[4]);      // 0: the run-time-length kernel for every frame size
+    AttnQuery q;
+    q.head_dim = hd; q.q_len = q.kv_len = (int)L; q.hq = q.hkv = heads;
+    q.ldq = a.ldq; q.ldk = a.ldk; q.ldv = a.ldv; q.ldo = a.ldo; q.head_stride = a.head_stride;
+    q.has_cu = true; q.nseg = nseg; q.max_seqlen = seg; q.uniform_seqlen = seg; q.q_prescaled = 1;
+    const AttnPlan plan = cogs_plan_attention_vit(q, tuning);
+    if (plan.status != COGS_OK) { printf("plan rejected the descriptor: %d\n", plan.status); return 1; }
+    printf("kernel %d, ragged end %d, grid (%d, %d, %d)\n", plan.kernel, plan.vit_end, plan.grid_x, plan.grid_y, plan.grid_z);
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
-    for (int i = 0; i < 3; ++i) cogs_k_attention_vit(0, a);
+    for (int i = 0; i < 3; ++i) cogs_k_attention_vit(0, a, plan);
     hipDeviceSynchronize();
     float best = 1e9f, sum = 0;
     for (int i = 0; i < 20; ++i) {
-        hipEventRecord(e0, 0); cogs_k_attention_vit(0, a); hipEventRecord(e1, 0); hipEventSynchronize(e1);
+        hipEventRecord(e0, 0); cogs_k_attention_vit(0, a, plan); hipEventRecord(e1, 0); hipEventSynchronize(e1);
         float ms; hipEventElapsedTime(&ms, e0, e1); best = ms < best ? ms : best; sum += ms;
     }
     const double fl = 4.0 * nseg * heads * (double)seg * seg * hd;
