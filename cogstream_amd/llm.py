@@ -10,7 +10,9 @@ import torch
 
 from . import _lib as L
 from . import beam as beam_host
+from . import decode
 from . import ops
+from .decode import host_draw_block, philox_offset, truncate_at_eos  # noqa: F401  (tests and callers import them from here)
 from .runtime import get_handle
 from .weights import LlmConfig, PackedLlm
 
@@ -30,27 +32,6 @@ def check_num_return_sequences(n: int, do_sample: bool, num_beams: int = 1) -> i
     if n > 1 and not do_sample:
         raise ValueError(f"Greedy methods without beam search do not support `num_return_sequences` different than 1 (got {n}).")
     return n
-
-
-def philox_offset(step: int, n_rows: int, row: int) -> int:
-    """sampler="device": the Philox offset of row `row` at step `step` of an n_rows-wide generate (= step at n_rows 1)"""
-    return step * n_rows + row
-
-
-def host_draw_block(generator, n_rows: int, vocab: int) -> torch.Tensor:
-    """sampler="host": the ONE [n_rows, vocab] Exponential(1) block torch.multinomial(probs[n_rows, vocab], 1) draws on the CPU
-    generator per step, row-major (row r of the block decides row r's token)"""
-    return torch.empty(n_rows, vocab, dtype=torch.float32).exponential_(1, generator=generator)
-
-
-def truncate_at_eos(rows: Sequence[Sequence[int]], eos) -> List[List[int]]:
-    """every row up to and including its first EOS"""
-    eos = set(int(e) for e in eos)
-    out = []
-    for r in rows:
-        hit = next((i for i, t in enumerate(r) if t in eos), None)
-        out.append(list(r) if hit is None else list(r[:hit + 1]))
-    return out
 
 
 def pad_rows(rows: Sequence[Sequence[int]], pad_token_id: int) -> torch.Tensor:
@@ -273,7 +254,8 @@ class Qwen2Engine:
                  stage_times: Optional[dict] = None, num_return_sequences: int = 1,
                  pad_token_id: Optional[int] = None, num_beams: int = 1, length_penalty: float = 1.0,
                  early_stopping=False):
-        """GenerationMixin.generate with inputs_embeds: prefill, then one cogs_llm_forward per token.
+        """GenerationMixin.generate with inputs_embeds: prefill, then one cogs_llm_forward per token (the token loop and the
+        ways a row advances are decode.py's: decode.sample, decode.SingleRow / Lockstep / Replay).
         Returns the NEW token ids only. Logits processors run in HF order:
         repetition penalty -> custom (allowed-id mask) -> temperature -> top-k -> top-p.
         `prefix`: reuse the KV rows of the leading embeddings that are unchanged since the previous call.
@@ -284,7 +266,7 @@ class Qwen2Engine:
         (`generator`, default the global one) makes the [vocab] exponential draws of every step exactly as
         torch.multinomial does in the reference's CPU run, so the sampled ids are the reference's.
         num_return_sequences = N > 1 (sampling only, N <= 16): N continuations of the one prefilled prompt, advanced in
-        lockstep by cogs_llm_decode_rows -> a list of N token lists (see _generate_rows); pad_token_id is accepted for
+        lockstep by cogs_llm_decode_rows -> a list of N token lists (see decode.sample); pad_token_id is accepted for
         signature parity with GenerationMixin (the lists are ragged; CogReasoner.generate pads).
         num_beams = B > 1 (2 .. 16, no sampling): beam search (see beam_search) -> the best hypothesis as a token list, or,
         for num_return_sequences = N <= B, the N best as a list of lists."""
@@ -295,11 +277,9 @@ class Qwen2Engine:
                                               repetition_penalty=repetition_penalty, allowed_ids=allowed_ids, prompt_ids=prompt_ids,
                                               cache=cache, ignore_eos=ignore_eos, prefix=prefix, prefilled=prefilled)
             return seqs[0] if int(num_return_sequences) == 1 else seqs
-        if check_num_return_sequences(num_return_sequences, do_sample) > 1:
-            return self._generate_rows(embeds, int(num_return_sequences), max_new_tokens=max_new_tokens, eos_token_id=eos_token_id,
-                                       temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
-                                       allowed_ids=allowed_ids, prompt_ids=prompt_ids, generator=generator, sampler=sampler,
-                                       seed=seed, cache=cache, ignore_eos=ignore_eos, prefix=prefix, prefilled=prefilled)
+        N = check_num_return_sequences(num_return_sequences, do_sample)
+        if N > 1:
+            stage_times = None             # the split is taken on the single-row path only, as before
         if stage_times is not None:        # bench.py's pipeline split: the prompt pass and the token loop, drained on both sides
             import time
             torch.cuda.synchronize()
@@ -309,53 +289,13 @@ class Qwen2Engine:
             torch.cuda.synchronize()
             t_loop = time.perf_counter()
             stage_times["answer_prefill"] = stage_times.get("answer_prefill", 0.0) + t_loop - t_start
-        allowed = (torch.tensor(list(allowed_ids), dtype=torch.int32, device=self.device) if allowed_ids is not None else None)
-        eos = set(int(e) for e in eos_token_id)
-        # token ids stay on the device: the greedy id feeds the next embedding gather and the repetition-penalty
-        # history without a host round trip; the host only looks at them every `check_every` steps (EOS test).
-        n_prompt = int(prompt_ids.numel()) if prompt_ids is not None else 0
-        seen = torch.empty(n_prompt + max_new_tokens, dtype=torch.int64, device=self.device)
-        if n_prompt:
-            seen[:n_prompt] = prompt_ids.reshape(-1).to(self.device)
-        toks = seen[n_prompt:]        # the generated ids ARE the tail of the penalty history: argmax / the sampler write them once
-        n_seen, produced = n_prompt, 0
-        # host-drawn sampling (parity mode) consumes one [vocab] draw of the CPU generator per step: steps issued past
-        # the EOS would advance that generator beyond where GenerationMixin stops, so the stop test runs every step
-        check_every = 1 if (do_sample and sampler == "host") else 8
-        if do_sample and sampler == "device" and seed is None:
-            seed = int(torch.randint(0, 2 ** 62, (1,), generator=generator).item())
-        need_proc = repetition_penalty != 1.0 or allowed is not None     # the temperature is applied inside cogs_sample
-        stop_at = None
-        for step in range(max_new_tokens):
-            logits = res["logits"]
-            if need_proc:
-                prev = seen[:n_seen] if (n_seen and repetition_penalty != 1.0) else None
-                ops.logits_process(logits, prev, repetition_penalty, allowed, 1.0)
-            if do_sample:
-                tok_dev = ops.sample(logits, top_k or 0, 1.0 if top_p is None else top_p,
-                                     draws=self._draws(generator) if sampler == "host" else None,
-                                     seed=seed or 0, offset=step, temperature=temperature, out=toks[step:step + 1])
-            else:
-                tok_dev = ops.argmax(logits, out=toks[step:step + 1])      # straight into the generated-ids buffer
-            n_seen += 1
-            produced += 1
-            last = step + 1 == max_new_tokens
-            if eos and not ignore_eos and ((step + 1) % check_every == 0 or last):
-                host = toks[:produced].tolist()
-                hit = next((i for i, t in enumerate(host) if t in eos), None)
-                if hit is not None:
-                    stop_at = hit + 1
-                    break
-            if not last:
-                res = self.forward(self.embed_tokens(tok_dev), cache)
-        out = toks[:produced].tolist()
+        rows = decode.sample(self, res["logits"], cache, pos_start, N, max_new_tokens=max_new_tokens, eos_token_id=eos_token_id,
+                             ignore_eos=ignore_eos, do_sample=do_sample, temperature=temperature, top_k=top_k, top_p=top_p,
+                             repetition_penalty=repetition_penalty, allowed_ids=allowed_ids, prompt_ids=prompt_ids,
+                             generator=generator, sampler=sampler, seed=seed)
         if stage_times is not None:
             stage_times["decode"] = stage_times.get("decode", 0.0) + time.perf_counter() - t_loop
-        if stop_at is not None:
-            out = out[:stop_at]
-            # forwards issued past the EOS only wrote KV rows that are dropped again here
-            cache.reset(min(cache.len, pos_start + stop_at - 1))
-        return out
+        return rows[0] if N == 1 else rows
 
     def decode_rows(self, embeds: torch.Tensor, kv: "L.KVRows", tail_slot: Optional[torch.Tensor] = None) -> torch.Tensor:
         """cogs_llm_decode_rows: one token per sequence, embeddings [R, H] -> fp32 logits [R, vocab]; advances kv.tail_len.
@@ -399,86 +339,39 @@ class Qwen2Engine:
                     select_fn=None):
         """GenerationMixin.generate(num_beams=B, do_sample=False) on one prefilled prompt -> (the num_return_sequences best
         hypotheses as lists of new token ids, their length-penalised scores); the bookkeeping is beam.beam_search.
-        bf16 / head_dim 128: the B beams advance in lockstep (cogs_llm_decode_rows_slots). A beam's K / V rows stay in the tail
-        slot that wrote them; per step the int32 [B, t] slot table is reordered by the beams' parents (slot = slot[parents];
-        slot[:, t] = arange(B)) and the attention reads every tail through it -- nothing of the KV moves. The token histories of
-        the repetition penalty are reordered the same way. Then cogs_row_lse + cogs_sub_rows turn the step's logits into
-        log-probabilities in place, cogs_logits_process runs per row when a penalty or mask is on (HF applies its processors to the
-        log-probabilities in beam search), and cogs_beam_topk selects the candidates with row_add = the beam scores; the
-        candidates' (value, row, token) triples are the step's one read-back. The debug switch beam_gather_tails = 1 copies
-        the tails by parent instead and passes no table (tests: the two must agree bit for bit).
-        fp32 engines / head_dim != 128: the same loop over single-row steps, one private K / V copy per beam, gathered by
-        parent. The shared cache is left at the prompt length, so a PrefixKV stays valid. select_fn: ops.beam_topk."""
+        The beams advance on a rows stepper of decode.py (decode.rows_stepper). bf16 / head_dim 128, decode.Lockstep: one
+        cogs_llm_decode_rows_slots per step, a beam's K / V rows stay in the tail slot that wrote them and the int32 [B, t] slot
+        table follows the beams' parents -- nothing of the KV moves (the debug switch beam_gather_tails = 1 copies the tails by
+        parent instead; tests: the two must agree bit for bit). fp32 engines / head_dim != 128, decode.Replay: single-row steps,
+        one private K / V copy per beam, gathered by parent. The token histories of the repetition penalty (decode.History) are
+        reordered the same way. Then cogs_row_lse + cogs_sub_rows turn the step's logits into log-probabilities in place,
+        cogs_logits_process runs per row when a penalty or mask is on (HF applies its processors to the log-probabilities in
+        beam search), and cogs_beam_topk selects the candidates with row_add = the beam scores; the candidates' (value, row,
+        token) triples are the step's one read-back. The shared cache is left at the prompt length, so a PrefixKV stays valid.
+        select_fn: ops.beam_topk."""
         eos = [] if ignore_eos else sorted(set(int(e) for e in eos_token_id))
         B = beam_host.check_beam_args(num_beams, num_return_sequences, do_sample, len(eos))
         N = check_num_return_sequences(num_return_sequences, do_sample, B)
         res, cache, _ = self._prefill(embeds, max_new_tokens, cache, prefix, prefilled)
-        P = cache.len
-        V = self.cfg.vocab_size
-        dev = self.device
-        allowed = (torch.tensor(list(allowed_ids), dtype=torch.int32, device=dev) if allowed_ids is not None else None)
-        n_prompt = int(prompt_ids.numel()) if prompt_ids is not None else 0
-        state = {"seen": torch.zeros(B, n_prompt + max(max_new_tokens, 1), dtype=torch.int64, device=dev), "t": 0}
-        if n_prompt:
-            state["seen"][:, :n_prompt] = prompt_ids.reshape(1, -1).to(dev)
-        need_proc = repetition_penalty != 1.0 or allowed is not None
+        V, dev = self.cfg.vocab_size, self.device
+        hist = decode.History(self, B, max(max_new_tokens, 1), prompt_ids, repetition_penalty, allowed_ids, alloc=torch.zeros)
+        stepper = decode.rows_stepper(self, cache, B, max(max_new_tokens, 1), slots=True)
 
         def logprobs(logits):                       # fp32 [rows, V] logits -> log-probabilities, in place
             return ops.sub_rows(logits, ops.row_lse(logits)["lse"])
 
         def process(scores, t):
-            if need_proc:
+            if hist.on:
                 for r in range(scores.shape[0]):
-                    prev = state["seen"][r, :n_prompt + t] if (n_prompt + t and repetition_penalty != 1.0) else None
-                    ops.logits_process(scores[r], prev, repetition_penalty, allowed, 1.0)
+                    hist.process(scores[r], r, t)
             return scores
 
-        def advance(tokens, parents):               # the histories follow the beams; -> (tokens, parents) on the device, position
-            j = state["t"]
+        def step(tokens, parents):                  # the histories follow the beams, then the K / V rows do
             par = torch.tensor(parents, dtype=torch.int64, device=dev)
             tok = torch.tensor(tokens, dtype=torch.int64, device=dev)
-            state["seen"] = state["seen"].index_select(0, par)
-            state["seen"][:, n_prompt + j] = tok
-            state["t"] = j + 1
-            return tok, par, j
-
-        lockstep = self.dtype == torch.bfloat16 and self.cfg.head_dim == 128
-        if lockstep:
-            kv, tail_k, tail_v, slot = self.new_rows_kv(cache, B, max(max_new_tokens, 1), slots=True)
-            gather = L.debug_get("beam_gather_tails") != 0
-            ident = torch.arange(B, dtype=torch.int32, device=dev)
-            tab = {"slot": slot}
-
-            def step(tokens, parents):
-                tok, par, j = advance(tokens, parents)
-                if gather:
-                    if j:
-                        tail_k[:, :, :j] = tail_k[:, par, :j]
-                        tail_v[:, :, :j] = tail_v[:, par, :j]
-                    table = None
-                else:
-                    table = tab["slot"].index_select(0, par)
-                    table[:, j] = ident
-                    tab["slot"] = table
-                return logprobs(self.decode_rows(self.embed_tokens(tok), kv, table))
-        else:
-            # per-beam private K / V rows [B][layers][max_new_tokens][kv_dim], replayed behind the prompt for each single-row step
-            # (the shape of _generate_rows's fallback) and gathered by parent
-            own = {"k": torch.empty((B, cache.k.shape[0], max(max_new_tokens, 1), cache.k.shape[2]), device=dev, dtype=self.dtype)}
-            own["v"] = torch.empty_like(own["k"])
-
-            def step(tokens, parents):
-                tok, par, j = advance(tokens, parents)
-                own["k"], own["v"] = own["k"].index_select(0, par), own["v"].index_select(0, par)
-                out = torch.empty(B, V, device=dev, dtype=torch.float32)
-                for r in range(B):
-                    cache.k[:, P:P + j] = own["k"][r, :, :j]
-                    cache.v[:, P:P + j] = own["v"][r, :, :j]
-                    cache.reset(P + j)
-                    out[r] = self.forward(self.embed_tokens(tok[r:r + 1]), cache)["logits"]
-                    own["k"][r, :, j] = cache.k[:, P + j]
-                    own["v"][r, :, j] = cache.v[:, P + j]
-                return logprobs(out)
+            hist.reorder(par)
+            hist.seen[:, hist.n_prompt + stepper.t] = tok
+            return logprobs(stepper.step(tok, par))
 
         def select(scores, row_add, k):             # the candidates come back in ONE copy: the step's synchronisation
             val, crow, ctok = (select_fn or ops.beam_topk)(scores, row_add, k)
@@ -493,115 +386,5 @@ class Qwen2Engine:
                                                  eos_token_id=eos, pad_token_id=pad_token_id, length_penalty=length_penalty,
                                                  early_stopping=early_stopping, num_return_sequences=N, process_fn=process)
         finally:
-            cache.reset(P)
+            stepper.close()
         return seqs, scores
-
-    def _generate_rows(self, embeds, N, *, max_new_tokens, eos_token_id, temperature, top_k, top_p, repetition_penalty,
-                       allowed_ids, prompt_ids, generator, sampler, seed, cache, ignore_eos, prefix, prefilled) -> List[List[int]]:
-        """GenerationMixin._sample on the N times expanded prompt, without expanding it: the prompt is prefilled once, the
-        first token of every row is drawn from the one processed prefill logits row, and the rows then advance in lockstep
-        (one multi-row step per token: every weight byte once per step) with their own repetition-penalty histories.
-        Row r of step s draws with Philox offset s * N + r (device sampler) or from row r of the step's [N, vocab] block of
-        the CPU generator (host sampler: what torch.multinomial on [N, vocab] consumes). A row that has produced an EOS is
-        cut there; it keeps being stepped until every row is done (rows do not influence one another). The shared cache is
-        left at the prompt length, so a PrefixKV stays valid. fp32 engines / head_dim != 128 have no multi-row kernels:
-        the same draws are made with single-row steps, one cache replayed per row and step."""
-        res, cache, _ = self._prefill(embeds, max_new_tokens, cache, prefix, prefilled)
-        P = cache.len                                   # the shared prompt: rows 0 .. P-1 of the cache
-        V = self.cfg.vocab_size
-        allowed = (torch.tensor(list(allowed_ids), dtype=torch.int32, device=self.device) if allowed_ids is not None else None)
-        eos = set() if ignore_eos else set(int(e) for e in eos_token_id)
-        n_prompt = int(prompt_ids.numel()) if prompt_ids is not None else 0
-        seen = torch.empty(N, n_prompt + max_new_tokens, dtype=torch.int64, device=self.device)
-        if n_prompt:
-            seen[:, :n_prompt] = prompt_ids.reshape(1, -1).to(self.device)
-        toks = seen[:, n_prompt:]
-        host = sampler == "host"
-        if not host and seed is None:
-            seed = int(torch.randint(0, 2 ** 62, (1,), generator=generator).item())
-        need_proc = repetition_penalty != 1.0 or allowed is not None
-        top_p = 1.0 if top_p is None else top_p
-
-        def process(row_logits, r, n_seen):
-            if need_proc:
-                prev = seen[r, :n_seen] if (n_seen and repetition_penalty != 1.0) else None
-                ops.logits_process(row_logits, prev, repetition_penalty, allowed, 1.0)
-
-        def draw(row_logits, r, step, block):
-            ops.sample(row_logits, top_k or 0, top_p, draws=block[r] if host else None, seed=seed or 0,
-                       offset=philox_offset(step, N, r), temperature=temperature, out=toks[r, step:step + 1])
-
-        def done_rows(produced):
-            rows = toks[:, :produced].tolist()
-            return rows, all(any(t in eos for t in r) for r in rows) if eos else False
-
-        first = res["logits"]
-        process(first, 0, n_prompt)                     # every row has the same history so far: processed once
-        if max_new_tokens <= 0:
-            return [[] for _ in range(N)]
-
-        if self.dtype != torch.bfloat16 or self.cfg.head_dim != 128:
-            # sequential fallback, step-outer like the lockstep loop, so a step's [N, vocab] block of host draws is made, used
-            # and dropped within the step. The one cache is replayed per row: row r's private K/V rows (kept aside in
-            # tk / tv, [N][layers][max_new_tokens][kv_dim]) are copied behind the prompt, the single-row step appends one
-            # more, and that one is copied back. A row that has produced an EOS is no longer stepped.
-            tk = torch.empty((N, cache.k.shape[0], max_new_tokens, cache.k.shape[2]), device=self.device, dtype=self.dtype)
-            tv = torch.empty_like(tk)
-            live = list(range(N))
-            produced = 0
-            for step in range(max_new_tokens):
-                block = host_draw_block(generator, N, V).to(self.device, non_blocking=True) if host else None
-                for r in live:
-                    if step == 0:
-                        logits = first.clone()
-                    else:
-                        t = step - 1                     # private rows 0 .. t-1 are in tk[r]; this step appends row t
-                        cache.k[:, P:P + t] = tk[r, :, :t]
-                        cache.v[:, P:P + t] = tv[r, :, :t]
-                        cache.reset(P + t)
-                        logits = self.forward(self.embed_tokens(toks[r, step - 1:step]), cache)["logits"]
-                        tk[r, :, t] = cache.k[:, P + t]
-                        tv[r, :, t] = cache.v[:, P + t]
-                        process(logits, r, n_prompt + step)
-                    draw(logits, r, step, block)
-                produced = step + 1
-                if eos and (host or produced % 8 == 0) and produced < max_new_tokens:
-                    got = toks[:, :produced].tolist()
-                    live = [r for r in live if not any(t in eos for t in got[r])]
-                    if not live:
-                        break
-            cache.reset(P)
-            return truncate_at_eos(toks[:, :produced].tolist(), eos)
-
-        kv, tail_k, tail_v = self.new_rows_kv(cache, N, max_new_tokens)
-        check_every = 1 if host else 8
-        produced = 0
-        rows = None
-        for step in range(max_new_tokens):
-            block = host_draw_block(generator, N, V).to(self.device, non_blocking=True) if host else None
-            if step == 0:
-                for r in range(N):
-                    draw(first.clone(), r, 0, block)
-            else:
-                logits = self.decode_rows(self.embed_tokens(toks[:, step - 1].contiguous()), kv)
-                for r in range(N):
-                    process(logits[r], r, n_prompt + step)
-                    draw(logits[r], r, step, block)
-            produced = step + 1
-            last = produced == max_new_tokens
-            if eos and (produced % check_every == 0 or last):
-                rows, done = done_rows(produced)
-                if done:
-                    break
-                rows = None
-        if rows is None:
-            rows = toks[:, :produced].tolist()
-        del tail_k, tail_v
-        cache.reset(P)
-        return truncate_at_eos(rows, eos)
-
-    def _draws(self, generator) -> torch.Tensor:
-        """parity mode: the [vocab] Exponential(1) draws torch.multinomial(probs, 1) makes on the CPU generator
-        (GenerationMixin._sample, transformers 4.46.3; the reference's CPU path draws from the global generator)"""
-        q = torch.empty(self.cfg.vocab_size, dtype=torch.float32).exponential_(1, generator=generator)
-        return q.to(self.device, non_blocking=True)
