@@ -116,6 +116,7 @@ cogs_status cogs_debug_get(const char* name, int64_t* value) {
     if (strcmp(name, "lm_score_last_rows") == 0) { *value = g_cogs_debug.lm_score_last_rows; return COGS_OK; }
     if (strcmp(name, "lm_score_last_cols") == 0) { *value = g_cogs_debug.lm_score_last_cols; return COGS_OK; }
     if (strcmp(name, "llm_last_decode_fp8") == 0) { *value = g_cogs_debug.llm_last_decode_fp8; return COGS_OK; }
+    if (strcmp(name, "sample_last_path") == 0) { *value = g_cogs_debug.sample_last_path; return COGS_OK; }
     return COGS_E_INVALID;
 }
 
@@ -133,7 +134,9 @@ const char* cogs_debug_list(void) {
         "lm_score_last_split / lm_score_last_chunk / lm_score_last_rows / lm_score_last_cols (read only): the last cogs_lm_score / "
         "cogs_row_lse -- workgroups per row of a full panel in the fold kernel (1: no column split), columns per workgroup, rows and "
         "columns of a panel\n"
-        "llm_last_decode_fp8 (read only): 1 the last cogs_llm_forward / cogs_llm_forward_segments took the e4m3 GEMVs, 0 the weights' own type\n";
+        "llm_last_decode_fp8 (read only): 1 the last cogs_llm_forward / cogs_llm_forward_segments took the e4m3 GEMVs, 0 the weights' own type\n"
+        "sample_last_path (read only): path of the last cogs_sample -- 1 slice top-k + merge (0 < top_k <= 64, 64 top_k <= n <= 262144), "
+        "2 whole-row radix selects\n";
 }
 
 cogs_status cogs_create(int device, cogs_handle* out) {

@@ -79,5 +79,7 @@ struct CogsDebug {
     std::atomic<long long> lm_score_last_cols{0};
     // ... and whether the last cogs_llm_forward / _segments took the e4m3 GEMVs (1) or the weights' own dtype (0)
     std::atomic<long long> llm_last_decode_fp8{0};
+    // ... and which path the last cogs_sample took: 0 none yet, 1 slice top-k + merge (0 < top_k <= 64), 2 whole-row
+    std::atomic<long long> sample_last_path{0};
 };
 extern CogsDebug g_cogs_debug;     // capi.hip

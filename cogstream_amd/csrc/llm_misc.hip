@@ -128,10 +128,12 @@ __global__ __launch_bounds__(1024) void topk_kernel(const float* __restrict__ lo
         if (tid == 0) {
             for (int w = 1; w < 16; ++w)
                 if (sv[w] > bv || (sv[w] == bv && si[w] < bi)) { bv = sv[w]; bi = si[w]; }
+            // -inf == -inf holds, so a scan over nothing but -inf (taken or masked entries) ends on the lowest index, not on
+            // "none": past the finite entries the tail is (-inf, -1); the host treats that as "fewer than k candidates"
+            if (bv == -INFINITY) bi = 0x7fffffff;
             tv[r] = bv;
             ti[r] = bi == 0x7fffffff ? -1 : bi;
             if (bi != 0x7fffffff) work[bi] = -INFINITY;
-            // a row of all -inf keeps returning -1; the host treats that as "fewer than k candidates"
         }
         __syncthreads();
     }

@@ -12,10 +12,18 @@
 // over (parity mode: the sampled ids then equal the reference's for the same generator state); with draws ==
 // NULL the kernel makes its own q_i = -log(u_i), u_i from Philox4x32-10 keyed by (seed, offset, i).
 //
-// Two paths: 0 < top_k <= 64 (the shipped default): 64 workgroups each reduce a slice of the row to its top_k
-// candidates, one workgroup merges 64 x top_k candidates and samples (2 launches, ~10 us). Otherwise (no top-k,
-// or top_k > 64): one workgroup works on the whole row with radix selects (exact for any k and any top_p).
+// Two paths (cogs_debug_get "sample_last_path"; the contract of both is stated once, at cogs_sample in include/cogs.h):
+// 1: 0 < top_k <= 64 and 64 top_k <= n <= 262144 (the shipped default): 64 workgroups each reduce a slice of the row to its
+//    top_k candidates, one workgroup merges 64 x top_k candidates and samples (2 launches, ~10 us). The kept list is
+//    ordered (score descending, id ascending) and top-p cuts it by position, so the kept count is HF's. A slice hands over
+//    at most top_k candidates and the list holds at most 1024: ties of the k-th value beyond that are dropped.
+// 2: otherwise (no top-k, top_k > 64, or a row too short / too long for 1): one workgroup works on the whole row with
+//    radix selects, for any k and any top_p. Both selections are thresholds on a VALUE, so every entry tied with the k-th
+//    score stays (as in HF) and every entry whose probability equals the top-p boundary probability stays (HF cuts inside
+//    such a block by sort position, which its unstable sort leaves open): on boundary ties this path keeps more than HF.
+// -0.0 orders as +0.0 on both paths (HF compares with IEEE <). NaN scores are not supported.
 #include "common.h"
+#include "debug.h"
 #include "kernels.h"
 
 namespace {
@@ -24,8 +32,9 @@ constexpr int SA_BLOCKS = 64;    // slices of the row in the fast path
 constexpr int SA_SLICE = 4096;   // max entries per slice (n <= 262144)
 constexpr int SA_KMAX = 64;
 
-__device__ __forceinline__ uint32_t fkey(float s) {   // order-preserving float -> uint
-    const uint32_t b = __float_as_uint(s);
+__device__ __forceinline__ uint32_t fkey(float s) {   // order-preserving float -> uint; -0 counts as +0, as under IEEE <
+    uint32_t b = __float_as_uint(s);
+    if (b == 0x80000000u) b = 0u;
     return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
 __device__ __forceinline__ float fkey_inv(uint32_t k) {
@@ -113,7 +122,7 @@ __global__ __launch_bounds__(1024) void sample_merge_kernel(const uint32_t* __re
     __shared__ __attribute__((aligned(16))) uint32_t ck[SA_BLOCKS * SA_KMAX];
     __shared__ __attribute__((aligned(16))) int ci[SA_BLOCKS * SA_KMAX];
     constexpr int KEPT_MAX = 1024;                  // top_k + ties of the k-th value (more ties than that are dropped)
-    __shared__ uint32_t sk[KEPT_MAX];               // kept, sorted: rank < k first, then ties with the k-th value
+    __shared__ uint32_t sk[KEPT_MAX];               // kept, at its rank (key descending, index ascending): the k-th value's ties follow rank k - 1
     __shared__ int si[KEPT_MAX];
     __shared__ int m_sh, ties_sh;
     __shared__ uint32_t t0_sh;
@@ -187,9 +196,9 @@ __global__ __launch_bounds__(1024) void sample_merge_kernel(const uint32_t* __re
         for (int j = tid; j < nc; j += 1024) {
             if (ck[j] != thr) continue;
             const int rank = rank_of(ck[j], ci[j]);
-            if (rank >= k) {
-                const int s = atomicAdd(&ties_sh, 1);
-                if (k + s < KEPT_MAX) { sk[k + s] = ck[j]; si[k + s] = ci[j]; }
+            if (rank >= k) {   // everything above thr ranks below k, so the ties fill ranks k .. k + ties - 1 without a gap
+                atomicAdd(&ties_sh, 1);
+                if (rank < KEPT_MAX) { sk[rank] = ck[j]; si[rank] = ci[j]; }
             }
         }
     }
@@ -412,12 +421,14 @@ int cogs_k_sample(hipStream_t st, const float* logits, int n, float temperature,
     const float lim = top_p >= 1.0 ? 0.0f : (float)(1.0 - top_p);
     if (top_k > 0 && top_k <= SA_KMAX && n <= SA_BLOCKS * SA_SLICE && n >= SA_BLOCKS * top_k) {
         if (!ws) return COGS_E_WORKSPACE;
+        g_cogs_debug.sample_last_path = 1;
         uint32_t* ck = (uint32_t*)ws;
         int* ci = (int*)(ck + SA_BLOCKS * SA_KMAX);
         hipLaunchKernelGGL(sample_slice_topk_kernel, dim3(SA_BLOCKS), dim3(256), 0, st, logits, n, top_k, temperature, ck, ci);
         hipLaunchKernelGGL(sample_merge_kernel, dim3(1), dim3(1024), 0, st, ck, ci, top_k, lim, draws, seed, offset,
                            out_token, kept_idx, kept_prob, n_kept, kept_cap);
     } else {
+        g_cogs_debug.sample_last_path = 2;
         hipLaunchKernelGGL(sample_full_kernel, dim3(1), dim3(1024), 0, st, logits, n, top_k, lim, temperature, draws, seed, offset,
                            out_token, kept_idx, kept_prob, n_kept, kept_cap);
     }

@@ -382,21 +382,17 @@ cogs_status cogs_preprocess_frames(cogs_stream stream, const uint8_t* frames, in
                                    void* out, int out_dtype, void* ws, size_t ws_bytes);
 
 /* logits post-processing (model/generation_config.json:2-12; qaselect_module_predict.py:86-103) */
+/* cogs_argmax: the FIRST maximum under IEEE == (+0 == -0), 0 on a row of -inf. cogs_logits_process, in place: repetition
+ * penalty (every id of prev once, whatever its multiplicity: s < 0 ? s * penalty : s / penalty), then the allowed-id mask
+ * (n_allowed <= 256, else COGS_E_INVALID; everything else becomes -inf), then / temperature -- each ONE fp32 IEEE operation.
+ * cogs_topk (1 <= top_k <= 1024, else COGS_E_INVALID): descending, equal values by ascending index; past the finite entries
+ * the tail is (-inf, -1). */
 cogs_status cogs_argmax(cogs_stream stream, const float* logits, int n, int64_t* out, void* ws /* >= 512 B */);
 cogs_status cogs_logits_process(cogs_stream stream, float* logits, int n, const int64_t* prev, int n_prev,
                                 float repetition_penalty, const int32_t* allowed, int n_allowed,
                                 float temperature, float* tmp /* >= n_prev floats */);
 cogs_status cogs_topk(cogs_stream stream, const float* logits, int n, int top_k, float* topk_val,
                       int32_t* topk_idx, float* ws /* >= n floats */);
-/* One sampled token from a PROCESSED fp32 row (after cogs_logits_process's penalty / mask): TemperatureLogitsWarper
- * (scores / temperature, temperature > 0; 1 = off) -> TopKLogitsWarper (top_k <= 0: off; keeps
- * every score >= the k-th largest) -> TopPLogitsWarper (top_p >= 1: off; ascending cumulative probability <= 1 - top_p
- * is dropped, the best token always stays) -> softmax -> torch.multinomial(probs, 1) = argmax_i probs_i / q_i,
- * q ~ Exp(1) (GenerationMixin._sample of transformers 4.46.3 with model/generation_config.json:2-12; call site
- * model/cogreasoner_chat.py:802-807). `draws`: NULL -> q_i from Philox4x32-10 keyed (seed, offset, i), no host round
- * trip; else device float [n] holding the CPU generator's exponential draws of this step (parity with the
- * reference's CPU sampler). Optional kept_idx/kept_prob [kept_cap] + n_kept report the surviving ids and their
- * renormalised probabilities (any order). ws >= cogs_sample_workspace_bytes(). */
 /* Per-row log-sum-exp, target logit and first-maximum argmax of fp32 logits [rows, n] (row stride ld elements; n and ld
  * multiples of 4, `logits` 16-byte aligned): what F.cross_entropy(logits, targets, ignore_index=-100, reduction="none")
  * and logits.argmax(-1) read out of the logits of Qwen2ForCausalLM.forward (behind model/cogreasoner_chat.py:680-693,
@@ -425,6 +421,31 @@ cogs_status cogs_beam_topk(cogs_stream stream, const float* scores, int rows, in
 /* x[r * ld + i] -= sub[r] (fp32 [rows, n] in place; n and ld multiples of 4, x 16-byte aligned): logits -> log-probabilities
  * with sub = the rows' lse of cogs_row_lse. */
 cogs_status cogs_sub_rows(cogs_stream stream, float* x, int rows, int n, int64_t ld, const float* sub);
+/* One sampled token from a PROCESSED fp32 row (after cogs_logits_process's penalty / mask): TemperatureLogitsWarper
+ * (v = scores / temperature, ONE fp32 IEEE division; temperature > 0, 1 = off) -> TopKLogitsWarper (top_k <= 0 or >= n: off;
+ * keeps every v >= the k-th largest) -> TopPLogitsWarper (top_p >= 1: off; the ascending cumulative probability <= fp32(1 -
+ * top_p) is dropped, the best token always stays, so top_p <= 0 keeps the best token only) -> softmax ->
+ * torch.multinomial(probs, 1) = argmax_i probs_i / q_i, q ~ Exp(1), the lower id on equal scores (GenerationMixin._sample of
+ * transformers 4.46.3 with model/generation_config.json:2-12; call site model/cogreasoner_chat.py:802-807). `draws`: NULL ->
+ * q_i = -logf(u), u = ((x >> 8) + 1) 2^-24 with x the first word of Philox4x32-10 under counter (i, offset low word, offset
+ * high word, 0) and key (seed low word, seed high word), no host round trip; else device float [n] holding the CPU generator's
+ * exponential draws of this step (parity with the reference's CPU sampler). ws >= cogs_sample_workspace_bytes().
+ * The contract where HF leaves the outcome to its unstable sort, by path (cogs_debug_get "sample_last_path"; the path is a
+ * function of (n, top_k) alone):
+ *  - path 1, 0 < top_k <= 64 and 64 top_k <= n <= 262144 (64 slices of ceil(n / 64) entries, then a merge): every entry tied
+ *    with the k-th value is kept, as in HF. The kept list is ordered by descending v, equal v by ascending id, and top-p cuts
+ *    it by position: the kept count is HF's, and a cut inside a block of equal v keeps the lower ids. Limits: a slice hands
+ *    over at most top_k candidates and the list holds at most 1024 entries, so with more than top_k ties of the k-th value
+ *    inside one slice, or more than 1024 kept, the surplus ties (highest ids first) are dropped; everything strictly above the
+ *    k-th value is kept, nothing below it, and n_kept >= top_k.
+ *  - path 2, every other (n, top_k) (one workgroup, radix selects): ties with the k-th value are all kept (HF), and so is
+ *    every entry whose probability equals the top-p boundary probability -- on a tie at that boundary more than HF keeps.
+ * Both: -0.0 counts as +0.0 (HF compares with IEEE <); entries at -inf (the allowed-id mask) are never kept, a row of nothing
+ * but -inf gives token 0 and n_kept 0; NaN scores are NOT supported. Optional kept_idx / kept_prob [kept_cap] + n_kept (all
+ * three and kept_cap > 0, or none) report the surviving ids and their renormalised probabilities: path 1 in the order above,
+ * path 2 in any order. *n_kept is the FULL survivor count; only the first min(n_kept, kept_cap) entries are written (path 2:
+ * any kept_cap of them). n <= 0, top_k < 0, temperature <= 0 or NaN, or an incomplete report triple: COGS_E_INVALID; path 1
+ * without ws: COGS_E_WORKSPACE; in both cases nothing is written. */
 size_t cogs_sample_workspace_bytes(void);
 cogs_status cogs_sample(cogs_stream stream, const float* logits, int n, float temperature, int top_k, double top_p,
                         const float* draws,
