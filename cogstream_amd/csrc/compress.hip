@@ -62,7 +62,9 @@ __global__ __launch_bounds__(256) void pixdiff_kernel(const T* __restrict__ pix,
     for (int e = (nch << 3) + lane; e < E; e += 64) acc += fabsf(rnd<T>(ld_f<T>(cur + e) - ld_f<T>(prv + e)));
     acc = wave_sum(acc);
     if (lane == 0) {
-        const float mean = rnd<T>(acc / (float)E);
+        // torch's mean on the device multiplies the sum by fp32(1 / E) (it does not divide): one ulp apart for some sums, and
+        // the reference's mask is made there
+        const float mean = rnd<T>(acc * (1.0f / (float)E));
         const float v = rnd<T>(mean * 255.0f);
         mask[w] = v > rnd<T>(thr) ? 1 : 0;
     }
