@@ -45,8 +45,8 @@ struct AttnArgs {
     int q_pos0;                     // causal: key j visible to query i iff j <= i + q_pos0
     int causal;
     int heavy_first;                // causal, one sequence: query tiles in descending order
-    int prio_mode;                  // prompt kernel (COGS_ATTN_PRIO): 1 = s_setprio 1 around the MFMA blocks, 2 (default) = around the softmax: the two
-                                    // waves of a SIMD, which belong to different workgroups, fall out of step, one's MFMAs beside the other's VALU
+    int layout_pad = 0;             // read by no kernel (was the prompt kernel's run-time priority mode): it keeps the argument offsets, without
+                                    // it hipcc groups the general kernels' scalar argument loads differently and they take one more SGPR
     int nsplit;                     // >1: keys split over blocks, partials go to part_o/part_ml
     int gqa_pack;                   // decode: the q-heads of one kv head are the 16 query columns
     int q_prescaled;                // Q already carries scale*log2(e): use the PRE kernels
@@ -531,19 +531,19 @@ __global__ __launch_bounds__(128 * (4 / NQ), NQ == 1 ? 4 : ((PRE && HD == 72) ? 
 // prefetch in front of every transposing read); cogstream_amd/build.py checks that nothing else in the kernel touches M0.
 __device__ __forceinline__ int v_swz(int row) { return ((row & 3) | (((row >> 3) & 1) << 2)) << 1; }
 
-// DEEP (round 5): the fragment reads of the interior tiles are ordered by hand. hipcc issues every K / V fragment
+// The fragment reads of the interior tiles are ordered by hand (round 5). hipcc issues every K / V fragment
 // read right before the MFMAs that consume it (ds_read, s_waitcnt, 2-4 MFMAs, ds_read, ...: prefetch distance 0-1), so a wave
 // stands for an LDS round trip (~100+ cycles) every 32-64 cycles of MFMA and the two waves of a SIMD can only half hide
 // each other -- the ~50 % MFMA-busy both this kernel and its ping-pong form show. sched_group_barrier pins an order with
 // the reads 6 (K) / 8 (V) instructions ahead of their MFMAs; hipcc still derives the counted s_waitcnt lgkmcnt(N).
-// DEEP also defers the running maximum (PREFILL_THR below). What bounds the kernel, measured on it
+// The running reference is deferred as well (PREFILL_THR below). What bounds the kernel, measured on it
 // (profiles/r5_prefill_attn_anatomy.txt): with every MFMA removed it still runs 1.20 of its 1.89 ms, and the MFMAs alone
 // would take 0.75 ms -- the two ADD: SQ_VALU_MFMA_BUSY_CYCLES + the VALU's active cycles are ~95 % of the resident time,
 // bank conflicts 0, LDS array 21 % busy, 2.4 % of wave time waiting for LDS.
+// Wave priority: s_setprio 1 over the softmax phase, 0 over the two MFMA blocks -- the two waves of a SIMD, which belong to
+// different workgroups, fall out of step, one's MFMAs beside the other's VALU. In-run A/B at 15 395 tokens, per layer: no
+// priority change 1.90-1.91 ms, raised around the MFMA blocks instead 1.88-1.89 ms, this scheme 1.83 ms.
 constexpr float PREFILL_THR = 6.f;
-// PRIO: the wave-priority scheme (debug switch attn_prio) as a compile-time choice -- 2 = raised in the softmax phase (shipped), -1 =
-// read p.prio_mode at run time (A/B runs: four s_cmp / s_cbranch pairs per tile, next to the MFMA blocks)
-template <int DEEP, int PRIO = -1>
 __global__ __launch_bounds__(256, 2) void attn_prefill_dma_kernel(AttnArgs p) {
     constexpr int HD = 128, NQ = 2, NT = 256, KS = 4, DT = 8;
     constexpr int K_LDS = 64 * 256, V_LDS = 64 * 256, BUF = K_LDS + V_LDS;     // 32 KiB per tile
@@ -589,7 +589,6 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_dma_kernel(AttnArgs p) {
 #pragma unroll
         for (int qi = 0; qi < NQ; ++qi) oacc[d][qi] = f32x4{0, 0, 0, 0};
     float l_run[NQ], m_ref[NQ];
-    bool first_tile_rt = true;      // round-4 form (DEEP = 0) only
 #pragma unroll
     for (int qi = 0; qi < NQ; ++qi) { l_run[qi] = 0.f; m_ref[qi] = 0.f; }
 
@@ -646,18 +645,17 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_dma_kernel(AttnArgs p) {
     const bool wave_active = q0 + wid * 32 < qe;
 
     // first_tag: the wave's first tile (kt == 0: it subtracts its own maximum explicitly) -- a compile-time copy, so that the
-    // other tiles carry no `first tile?` test (DEEP only; the round-4 form keeps the run-time flag)
+    // other tiles carry no `first tile?` test
     auto process_tile = [&](const int kt, auto masked_tag, auto first_tag) {
         constexpr bool MASKED = decltype(masked_tag)::value;
-        constexpr bool FIRST_CT = decltype(first_tag)::value;
-        const bool first_tile = DEEP ? FIRST_CT : first_tile_rt;
+        constexpr bool first_tile = decltype(first_tag)::value;
         const char* Ks = smem + (kt & 1) * BUF;
         const char* Vs = Ks + K_LDS;
         if (!wave_active) return;
         const int kbase = ks + kt * 64;
         const bool second_half = !MASKED || kbase + 32 < kend;
         f32x4 sacc[4][NQ];
-        { const int pm = PRIO >= 0 ? PRIO : p.prio_mode; if (pm == 1) __builtin_amdgcn_s_setprio(1); else if (pm == 2) __builtin_amdgcn_s_setprio(0); }
+        __builtin_amdgcn_s_setprio(0);
 #pragma unroll
         for (int ut = 0; ut < 4; ++ut) {
             if (MASKED && ut >= 2 && !second_half) {
@@ -679,7 +677,7 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_dma_kernel(AttnArgs p) {
                 }
             }
         }
-        if constexpr (DEEP && !MASKED) {          // 16 reads, 32 MFMAs: 6 reads, then a read per pair of MFMAs
+        if constexpr (!MASKED) {                  // 16 reads, 32 MFMAs: 6 reads, then a read per pair of MFMAs
             __builtin_amdgcn_sched_group_barrier(0x100, 6, 0);
 #pragma unroll
             for (int i = 0; i < 10; ++i) {
@@ -688,13 +686,11 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_dma_kernel(AttnArgs p) {
             }
             __builtin_amdgcn_sched_group_barrier(0x008, 12, 0);
         }
-        { const int pm = PRIO >= 0 ? PRIO : p.prio_mode; if (pm == 1) __builtin_amdgcn_s_setprio(0); else if (pm == 2) __builtin_amdgcn_s_setprio(1); }
+        __builtin_amdgcn_s_setprio(1);
         bf16x8 pf[2][NQ];
-        float post_alpha[NQ];
 #pragma unroll
         for (int qi = 0; qi < NQ; ++qi) {
             float sv[4][4];
-            post_alpha[qi] = 1.f;
             float d = -INFINITY;
             if constexpr (MASKED) {
                 const int qloc = qrow[qi] - qs;
@@ -714,8 +710,8 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_dma_kernel(AttnArgs p) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) { sv[ut][r] = sacc[ut][qi][r]; d = fmaxf(d, sacc[ut][qi][r]); }
             }
-            if (!DEEP || first_tile) d = colgroup_max(d);       // DEEP: d stays this lane's own maximum (4 of the row's 16 keys per block)
-            if (first_tile) {
+            if (first_tile) {                          // otherwise d stays this lane's own maximum (4 of the row's 16 keys per block)
+                d = colgroup_max(d);
                 const float d0 = (d == -INFINITY) ? 0.f : d;
 #pragma unroll
                 for (int ut = 0; ut < 4; ++ut)
@@ -725,17 +721,15 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_dma_kernel(AttnArgs p) {
                 m_ref[qi] = d0;
                 d = 0.f;
             }
-            // DEEP (the shipped form): the reference only moves when a score exceeds it by 2^PREFILL_THR (P <= 2^6 until then: exact in
+            // The reference only moves when a score exceeds it by 2^PREFILL_THR (P <= 2^6 until then: exact in
             // fp32 sums, the same relative precision in bf16); the test is wave-uniform on the lanes' OWN maxima, so the two lane
             // exchanges of colgroup_max and the rescale of O leave the common path (they ran in ~25 % of the tiles). Round 6: the move
-            // happens HERE, in front of the exponentials, for every threshold crossing -- one test per tile as before, and a key far
-            // above the reference can no longer make exp2 overflow before a deferred factor is applied (inf * 2^-dd = NaN).
-            // Round-4 form (DEEP = 0, A/B only): the deferred factor behind the PV product stays; only a crossing of more than
-            // 2^PRE_FAR takes this path.
-            constexpr float MOVE_THR = DEEP ? PREFILL_THR : PRE_FAR;
-            if (__any(d > MOVE_THR)) {
-                const float dr = DEEP ? colgroup_max(d) : d;
-                const float dd = dr > MOVE_THR ? dr : 0.f;
+            // happens HERE, in front of the exponentials, for every threshold crossing -- one test per tile, and a key far
+            // above the reference cannot make exp2 overflow before a factor deferred behind the PV product is applied
+            // (inf * 2^-dd = NaN).
+            if (__any(d > PREFILL_THR)) {
+                const float dr = colgroup_max(d);
+                const float dd = dr > PREFILL_THR ? dr : 0.f;
                 const float al = __builtin_amdgcn_exp2f(-dd);
 #pragma unroll
                 for (int ut = 0; ut < 4; ++ut)
@@ -757,13 +751,6 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_dma_kernel(AttnArgs p) {
                     psum += pv;
                 }
             l_run[qi] += psum;
-            if constexpr (DEEP) {
-                // (moved in front of the exponentials, above)
-            } else if (__any(d > 0.f)) {
-                const float dd = fmaxf(d, 0.f);
-                post_alpha[qi] = __builtin_amdgcn_exp2f(-dd);
-                m_ref[qi] += dd;
-            }
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
                 u32x4 w;
@@ -774,7 +761,7 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_dma_kernel(AttnArgs p) {
                 pf[u][qi] = __builtin_bit_cast(bf16x8, w);
             }
         }
-        { const int pm = PRIO >= 0 ? PRIO : p.prio_mode; if (pm == 1) __builtin_amdgcn_s_setprio(1); else if (pm == 2) __builtin_amdgcn_s_setprio(0); }
+        __builtin_amdgcn_s_setprio(0);
 #pragma unroll
         for (int d = 0; d < DT; ++d) {
 #pragma unroll
@@ -792,7 +779,7 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_dma_kernel(AttnArgs p) {
                     oacc[d][qi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[u][qi], oacc[d][qi], 0, 0, 0);
             }
         }
-        if constexpr (DEEP && !MASKED) {          // 32 transposed reads, 32 MFMAs: 8 reads lead (beside the exponentials)
+        if constexpr (!MASKED) {                  // 32 transposed reads, 32 MFMAs: 8 reads lead (beside the exponentials)
             __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);
 #pragma unroll
             for (int i = 0; i < 6; ++i) {
@@ -801,19 +788,7 @@ __global__ __launch_bounds__(256, 2) void attn_prefill_dma_kernel(AttnArgs p) {
             }
             __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
         }
-        if constexpr (!DEEP) {        // the deferred factor exists in the round-4 form only
-#pragma unroll
-        for (int qi = 0; qi < NQ; ++qi) {
-            if (__any(post_alpha[qi] != 1.f)) {
-                l_run[qi] *= post_alpha[qi];
-#pragma unroll
-                for (int d = 0; d < DT; ++d) oacc[d][qi] *= post_alpha[qi];
-            }
-        }
-        }
-        first_tile_rt = false;
     };
-
 
     // (Round 5 also built this loop with interior tiles as two 32-key halves pipelined INSIDE the tile -- S(h1) beside softmax(h0),
     // PV(h0) beside softmax(h1), pinned by sched_group_barrier -- and, as attn_prefill_sp_kernel, with S(t+1) beside softmax(t)
@@ -1055,8 +1030,7 @@ AttnTuning cogs_k_attention_tuning() {
     AttnTuning t;
     t.attn_vit = g_cogs_debug.attn_vit; t.attn_vit_early = g_cogs_debug.attn_vit_early; t.attn_vit_len = g_cogs_debug.attn_vit_len;
     t.attn_decode = g_cogs_debug.attn_decode; t.attn_combine32 = g_cogs_debug.attn_combine32;
-    t.attn_prefill_dma = g_cogs_debug.attn_prefill_dma; t.attn_prefill_deep = g_cogs_debug.attn_prefill_deep;
-    t.attn_prio = g_cogs_debug.attn_prio; t.attn_light_first = g_cogs_debug.attn_light_first; t.attn_nq = g_cogs_debug.attn_nq;
+    t.attn_prefill_dma = g_cogs_debug.attn_prefill_dma; t.attn_light_first = g_cogs_debug.attn_light_first; t.attn_nq = g_cogs_debug.attn_nq;
     t.llm_split_keys = g_cogs_debug.llm_split_keys;
     return t;
 }
@@ -1086,16 +1060,14 @@ int cogs_k_attention(hipStream_t st, const CogsAttn& a) {
     p.scale_log2 = a.q_prescaled ? 1.0f : a.scale * LOG2E;   // prescaled Q: scores are already in log2 units
     p.bias_log2 = a.bias * LOG2E;
     p.q_pos0 = a.q_pos0; p.causal = a.causal;
-    p.heavy_first = plan.heavy_first; p.prio_mode = plan.prio_mode;
+    p.heavy_first = plan.heavy_first;
     p.nsplit = plan.nsplit; p.gqa_pack = plan.gqa_pack; p.q_prescaled = plan.q_prescaled;
     p.part_o = plan.nsplit > 1 ? (float*)a.ws : nullptr;
     p.part_ml = plan.nsplit > 1 ? p.part_o + plan.part_ml_off : nullptr;
     const dim3 grid(plan.grid_x, plan.grid_y, plan.grid_z), block(plan.block_x);
     switch (plan.kernel) {
         case 5:
-            if (plan.deep && plan.prio_t == 2) hipLaunchKernelGGL((attn_prefill_dma_kernel<1, 2>), grid, block, 0, st, p);
-            else if (plan.deep) hipLaunchKernelGGL((attn_prefill_dma_kernel<1, -1>), grid, block, 0, st, p);
-            else hipLaunchKernelGGL((attn_prefill_dma_kernel<0, -1>), grid, block, 0, st, p);
+            hipLaunchKernelGGL(attn_prefill_dma_kernel, grid, block, 0, st, p);
             break;
         case 4: {
             const int rc = cogs_k_attention_decode(st, a, plan, p.part_o, p.part_ml);

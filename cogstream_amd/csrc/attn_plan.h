@@ -10,7 +10,7 @@
 // them: capi.hip turns it into the descriptor's uniform_seqlen)
 struct AttnTuning {
     long long attn_vit = 2, attn_vit_early = 0, attn_vit_len = 1, attn_decode = 1, attn_combine32 = 1, attn_prefill_dma = 1,
-              attn_prefill_deep = 1, attn_prio = 2, attn_light_first = 0, attn_nq = 0, llm_split_keys = 0;
+              attn_light_first = 0, attn_nq = 0, llm_split_keys = 0;
 };
 
 // what the decision depends on of a CogsAttn (kernels.h): no pointers, only whether they are there
@@ -44,13 +44,12 @@ struct AttnPlan {
     int kernel = 0;
     // the instantiation
     int hd = 0, nq = 0, pre = 0;         // kernel 1: attn_fwd_bf16_kernel<hd, nq, pre> (threads = block_x)
-    int deep = 0, prio_t = -1;           // kernel 5: attn_prefill_dma_kernel<deep, prio_t>
     int vit_pipe = 0, vit_r = 0, vit_nlb = 0;   // kernels 3 / 8: attn_vit_pipe_kernel<72, vit_r, vit_nlb> ...
     int vit_end = 0;                     //   ... and what attn_vit_last_end reports: 10 vit_r + vit_nlb (0: the run-time form)
     int rows_slot = 0;                   // multi-row step: attn_decode_kernel<true, rows_slot>
     int grid_x = 0, grid_y = 1, grid_z = 1, block_x = 0;
     // kernel arguments the launcher derives (AttnArgs / VitAttnArgs / DecodeAttnArgs)
-    int nsplit = 1, gqa_pack = 0, heavy_first = 0, prio_mode = 0, q_prescaled = 0;
+    int nsplit = 1, gqa_pack = 0, heavy_first = 0, q_prescaled = 0;
     int nqb = 0, uniform_len = 0, xcd_order = 0, early_prefetch = 0;
     long head_stride = 0;
     int kend = 0, gsz = 0, ntile = 1;    // decode kernels: visible (shared) keys, query heads per kv head, column tiles per kv head
@@ -161,7 +160,6 @@ inline AttnPlan cogs_plan_attention(const AttnQuery& q, const AttnTuning& t) {
     plan.gqa_pack = q.q_len == 1 && q.hq / q.hkv <= 16 && !q.has_cu;
     plan.grid_x = qtiles * plan.nsplit; plan.grid_y = plan.gqa_pack ? q.hkv : q.hq; plan.grid_z = plan.nseg;
     plan.heavy_first = (q.causal && !q.has_cu && q.q_len > 128 && t.attn_light_first != 1) ? 1 : 0;   // attn_light_first: A/B runs only
-    plan.prio_mode = (int)t.attn_prio;   // in-run A/B at 15 395 tokens: 0 / 1 / 2 = 1.90-1.91 / 1.88-1.89 / 1.83 ms per layer
     if (q.q_prescaled && q.has_row_lo) return reject(COGS_E_UNSUPPORTED);   // the bias mode is parity-only and unscaled
     const bool pre = q.q_prescaled != 0;
     plan.q_prescaled = pre;
@@ -175,8 +173,6 @@ inline AttnPlan cogs_plan_attention(const AttnQuery& q, const AttnTuning& t) {
         // (two more forms were built, tested at full size and measured slower -- a ping-pong form, 1.89 vs 1.81-1.86 ms per layer
         // at 15 395 tokens, and 64 query rows per wave, 2.94 vs 1.97 ms: tools/experiments/attn_prefill_variants.hip)
         plan.kernel = 5;
-        plan.deep = t.attn_prefill_deep != 0;
-        plan.prio_t = plan.deep && plan.prio_mode == 2 ? 2 : -1;
         plan.block_x = 256;
         return plan;
     }

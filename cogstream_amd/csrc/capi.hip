@@ -81,7 +81,7 @@ static bool cogs_debug_value_ok(const char* name, int64_t v) {
     struct Range { const char* name; int64_t lo, hi; };
     static const Range ranges[] = {
         {"gemm_wgs", 0, 256}, {"gemm_pad_pct", 100, 400}, {"gemm_group_m", 0, 64}, {"gemm_co_streams", 0, 8},
-        {"gemm_ring_cost_permille", 1, 4000}, {"gemv_small_n", 0, 1 << 30}, {"gemv_fp8_load", 8, 16}, {"attn_vit", 0, 2}, {"attn_uniform_hint", 0, 1 << 20}, {"attn_prio", 0, 2},
+        {"gemm_ring_cost_permille", 1, 4000}, {"gemv_small_n", 0, 1 << 30}, {"gemv_fp8_load", 8, 16}, {"attn_vit", 0, 2}, {"attn_uniform_hint", 0, 1 << 20},
         {"attn_nq", 0, 2}, {"vit_split_max", 0, INT64_MAX}, {"llm_split_keys", 0, 1 << 24}, {"km_row_groups", 0, 1 << 16},
         {"lm_score_rows", 1, 1 << 16}, {"lm_score_cols", 0, 1 << 24}, {"lm_score_split", 0, 4096},
     };

@@ -43,8 +43,6 @@
     X(attn_decode, 1, "0: single-token attention through the general split-KV kernel")                                      \
     X(attn_combine32, 1, "split-KV combine: 1 one block per (head, 32-column slice), 8 loads in flight per thread; 0 one block per head") \
     X(attn_prefill_dma, 1, "0: Qwen2 prompt attention through the general register-staged kernel")                          \
-    X(attn_prefill_deep, 1, "prompt LDS-DMA kernel: 1 fragment reads ordered 6-8 ahead of their MFMAs + running maximum deferred to 2^6 (round 5: 1.82 -> 1.64 ms), 0 the round-4 kernel") \
-    X(attn_prio, 2, "prompt attention wave priorities: 0 none, 1 MFMA phases raised, 2 softmax phase raised")               \
     X(attn_light_first, 0, "1: causal query tiles issued lightest first")                                                   \
     X(attn_nq, 0, "general kernel: 1 / 2 forces 16 / 32 query rows per wave")                                              \
     /* ---- encoder / LLM drivers (csrc/capi_vit.hip, capi_llm.hip), k-means */                                            \

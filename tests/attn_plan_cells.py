@@ -15,8 +15,7 @@ GUARD_ROWS = 5
 VIT_ENDS = {193: 41, 256: 42, 257: 51, 320: 52, 321: 61, 384: 62, 385: 71, 448: 72}      # tests/test_gpu_attn_conformance.py
 # the plan switches, each flipped alone (index 0: the shipped defaults)
 SWITCHED = [{}, {"attn_vit": 0}, {"attn_vit": 1}, {"attn_vit_len": 0}, {"attn_decode": 0}, {"attn_prefill_dma": 0},
-            {"attn_prefill_deep": 0}, {"attn_prio": 0}, {"attn_prio": 1}, {"attn_nq": 1}, {"attn_nq": 2}, {"attn_combine32": 0},
-            {"attn_light_first": 1}]
+            {"attn_nq": 1}, {"attn_nq": 2}, {"attn_combine32": 0}, {"attn_light_first": 1}]
 
 DEFAULTS = dict(kind="attn", dtype="bf16", hd=128, q_len=1, q_pos0=0, causal=0, pre=0, hq=4, hkv=4, nsplit=1, cu=None, row_lo=0,
                 force_rowwise=0, ws="exact", head_major=0, ldv_pad=0, ld_off=None, head_stride=None, hint=0)

@@ -2,10 +2,10 @@
 #include "attn_plan.h"
 
 namespace {
-constexpr int NT = 11;
+constexpr int NT = 9;
 long long* fields(AttnTuning& t, int i) {
     long long* f[] = {&t.attn_vit, &t.attn_vit_early, &t.attn_vit_len, &t.attn_decode, &t.attn_combine32, &t.attn_prefill_dma,
-                      &t.attn_prefill_deep, &t.attn_prio, &t.attn_light_first, &t.attn_nq, &t.llm_split_keys};
+                      &t.attn_light_first, &t.attn_nq, &t.llm_split_keys};
     return f[i];
 }
 AttnTuning tuning(const long long* v) {
@@ -14,25 +14,24 @@ AttnTuning tuning(const long long* v) {
     return t;
 }
 void put(const AttnPlan& p, long long* o) {
-    const long long v[] = {p.status, p.kernel, p.hd, p.nq, p.pre, p.deep, p.prio_t, p.vit_pipe, p.vit_r, p.vit_nlb, p.vit_end, p.rows_slot,
-                           p.grid_x, p.grid_y, p.grid_z, p.block_x, p.nsplit, p.gqa_pack, p.heavy_first, p.prio_mode, p.q_prescaled,
+    const long long v[] = {p.status, p.kernel, p.hd, p.nq, p.pre, p.vit_pipe, p.vit_r, p.vit_nlb, p.vit_end, p.rows_slot,
+                           p.grid_x, p.grid_y, p.grid_z, p.block_x, p.nsplit, p.gqa_pack, p.heavy_first, p.q_prescaled,
                            p.nqb, p.uniform_len, p.xcd_order, p.early_prefetch, p.head_stride, p.kend, p.gsz, p.ntile, p.combine,
                            p.combine_x, p.combine_y, p.combine_z, p.parts, (long long)p.ws_need, (long long)p.part_ml_off, p.nseg};
-    for (int i = 0; i < 37; ++i) o[i] = v[i];
+    for (int i = 0; i < 34; ++i) o[i] = v[i];
 }
 }  // namespace
 
 extern "C" const char* attn_tuning_names() {
-    return "attn_vit attn_vit_early attn_vit_len attn_decode attn_combine32 attn_prefill_dma attn_prefill_deep attn_prio "
-           "attn_light_first attn_nq llm_split_keys";
+    return "attn_vit attn_vit_early attn_vit_len attn_decode attn_combine32 attn_prefill_dma attn_light_first attn_nq llm_split_keys";
 }
 extern "C" void attn_tuning_defaults(long long* out) {
     AttnTuning t;
     for (int i = 0; i < NT; ++i) out[i] = *fields(t, i);
 }
 extern "C" const char* attn_plan_names() {
-    return "status kernel hd nq pre deep prio_t vit_pipe vit_r vit_nlb vit_end rows_slot grid_x grid_y grid_z block_x nsplit gqa_pack "
-           "heavy_first prio_mode q_prescaled nqb uniform_len xcd_order early_prefetch head_stride kend gsz ntile combine combine_x "
+    return "status kernel hd nq pre vit_pipe vit_r vit_nlb vit_end rows_slot grid_x grid_y grid_z block_x nsplit gqa_pack "
+           "heavy_first q_prescaled nqb uniform_len xcd_order early_prefetch head_stride kend gsz ntile combine combine_x "
            "combine_y combine_z parts ws_need part_ml_off nseg";
 }
 extern "C" const char* attn_query_names() {

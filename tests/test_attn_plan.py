@@ -84,7 +84,7 @@ def test_tuning_defaults_are_the_shipped_switch_defaults(shim):
     text = open(os.path.join(CSRC, "debug.h")).read()
     shipped = {m.group(1): int(m.group(2)) for m in re.finditer(r"X\((\w+), (-?\d+)(?:LL)?,", text)}
     t = tuning_defaults(shim)
-    assert len(t) == 11
+    assert len(t) == 9
     for name, value in t.items():
         assert shipped[name] == value, name
 
@@ -144,13 +144,11 @@ def test_cfg2_prompt_and_decode(shim):
     hq, hkv, hd, S = 28, 4, 128, 15395
     base = dict(head_dim=hd, hq=hq, hkv=hkv, ldq=(hq + 2 * hkv) * hd, ldk=hkv * hd, ldv=hkv * hd, ldo=hq * hd, causal=1, q_prescaled=1)
     p = plan(shim, query(q_len=S, kv_len=S, **base))
-    assert (p["status"], p["kernel"], p["deep"], p["prio_t"]) == (OK, 5, 1, 2), p
+    assert (p["status"], p["kernel"]) == (OK, 5), p
     assert (p["grid_x"], p["grid_y"], p["grid_z"], p["block_x"]) == (121, 28, 1, 256), p
-    assert (p["heavy_first"], p["prio_mode"], p["nsplit"], p["gqa_pack"], p["q_prescaled"], p["combine"]) == (1, 2, 1, 0, 1, COMBINE_NONE), p
-    # the other two instantiations, and the routing conditions no GPU cell exercises: O rows that are 8- but not 16-byte aligned
+    assert (p["heavy_first"], p["nsplit"], p["gqa_pack"], p["q_prescaled"], p["combine"]) == (1, 1, 0, 1, COMBINE_NONE), p
+    # the routing conditions no GPU cell exercises: O rows that are 8- but not 16-byte aligned
     # stay on the general kernel; a prompt behind a cached prefix stays on the prompt kernel whatever its length
-    assert [plan(shim, query(q_len=S, kv_len=S, **base), **sw)["prio_t"] for sw in ({"attn_prio": 0}, {"attn_prio": 1}, {"attn_prefill_deep": 0})] == [-1] * 3
-    assert plan(shim, query(q_len=S, kv_len=S, **base), attn_prefill_deep=0)["deep"] == 0
     assert plan(shim, query(q_len=S, kv_len=S, **base), attn_light_first=1)["heavy_first"] == 0
     assert plan(shim, query(q_len=S, kv_len=S, **{**base, "ldo": hq * hd + 4}))["kernel"] == 1
     p = plan(shim, query(q_len=5, kv_len=S + 5, q_pos0=S, **base))
@@ -233,3 +231,12 @@ def test_split_rule(shim):
 def test_plan_header_is_host_only():
     text = open(os.path.join(CSRC, "attn_plan.h")).read()
     assert "hip" not in "".join(l for l in text.splitlines() if l.lstrip().startswith("#include")).lower()
+
+
+def test_retired_attention_switches_are_unknown_names():
+    """attn_prefill_deep and attn_prio selected forms of the prompt kernel that no longer exist: the switch table answers them
+    like any other unknown name"""
+    from cogstream_amd import _lib as L
+    for name in ("attn_prefill_deep", "attn_prio"):
+        assert name not in L.debug_list()
+        assert L.lib.cogs_debug_set(name.encode(), 1) == L.E_INVALID, name

@@ -35,8 +35,7 @@ LN2_F32 = R.f32(math.log(2.0))
 
 REACHED: set = set()
 VIT_ENDS = {193: 41, 256: 42, 257: 51, 320: 52, 321: 61, 384: 62, 385: 71, 448: 72}
-PROMPT_VARIANTS = {"<1,2>": {}, "<1,-1> prio0": dict(attn_prio=0), "<1,-1> prio1": dict(attn_prio=1),
-                   "<0,-1>": dict(attn_prefill_deep=0)}
+PROMPT_VARIANTS = {"<1,2>": {}}
 REQUIRED = (
     [(5, f"{v} hf={hf}") for v in PROMPT_VARIANTS for hf in (0, 1)]
     + [(5, "varlen"), (5, "q_pos0 < 128 new rows"), (5, "15395")]
