@@ -179,6 +179,7 @@ SIGNATURES = {
     "cogs_profile_end": (c_int, [c_void_p, c_void_p, C.POINTER(c_float), C.POINTER(c_int)]),
     "cogs_gemm": (c_int, [c_void_p, C.POINTER(GemmDesc)]),
     "cogs_gemm_rows": (c_int, [c_void_p, C.POINTER(GemmDesc), c_float, c_int]),
+    "cogs_gemm_rows_fp8": (c_int, [c_void_p, C.POINTER(GemmDesc), c_void_p, c_float, c_int]),
     "cogs_attention_rows": (c_int, [c_void_p, C.POINTER(AttnRowsDesc)]),
     "cogs_llm_decode_rows_workspace_bytes": (c_int, [c_void_p, c_int, c_int, C.POINTER(c_size_t)]),
     "cogs_llm_decode_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int, C.POINTER(KVRows), c_void_p, c_void_p, c_size_t]),

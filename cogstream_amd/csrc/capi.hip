@@ -116,6 +116,7 @@ cogs_status cogs_debug_get(const char* name, int64_t* value) {
     if (strcmp(name, "lm_score_last_rows") == 0) { *value = g_cogs_debug.lm_score_last_rows; return COGS_OK; }
     if (strcmp(name, "lm_score_last_cols") == 0) { *value = g_cogs_debug.lm_score_last_cols; return COGS_OK; }
     if (strcmp(name, "llm_last_decode_fp8") == 0) { *value = g_cogs_debug.llm_last_decode_fp8; return COGS_OK; }
+    if (strcmp(name, "llm_last_rows_fp8") == 0) { *value = g_cogs_debug.llm_last_rows_fp8; return COGS_OK; }
     if (strcmp(name, "sample_last_path") == 0) { *value = g_cogs_debug.sample_last_path; return COGS_OK; }
     return COGS_E_INVALID;
 }
@@ -134,7 +135,10 @@ const char* cogs_debug_list(void) {
         "lm_score_last_split / lm_score_last_chunk / lm_score_last_rows / lm_score_last_cols (read only): the last cogs_lm_score / "
         "cogs_row_lse -- workgroups per row of a full panel in the fold kernel (1: no column split), columns per workgroup, rows and "
         "columns of a panel\n"
-        "llm_last_decode_fp8 (read only): 1 the last cogs_llm_forward / cogs_llm_forward_segments took the e4m3 GEMVs, 0 the weights' own type\n"
+        "llm_last_decode_fp8 (read only): 1 the last cogs_llm_forward / cogs_llm_forward_segments took the e4m3 GEMVs, 0 the weights' own type "
+        "(single-token forwards only: the multi-row step sets it to 0 and reports in llm_last_rows_fp8)\n"
+        "llm_last_rows_fp8 (read only): 1 the last cogs_llm_decode_rows / cogs_llm_decode_rows_slots streamed the attached e4m3 codes "
+        "(cogs_gemm_rows_fp8), 0 the (dequantised) matrices of cogs_llm_weights\n"
         "sample_last_path (read only): path of the last cogs_sample -- 1 slice top-k + merge (0 < top_k <= 64, 64 top_k <= n <= 262144), "
         "2 whole-row radix selects\n";
 }
@@ -200,6 +204,13 @@ cogs_status cogs_gemm_rows(cogs_stream stream, const cogs_gemm_desc* d, float q_
     CogsGemm g = to_gemm(d);
     if (q_scale != 0.f) { g.q_scale = q_scale; g.q_cols = q_cols; }
     return cogs_k_gemm_rows((hipStream_t)stream, g);
+}
+
+cogs_status cogs_gemm_rows_fp8(cogs_stream stream, const cogs_gemm_desc* d, const float* scale, float q_scale, int q_cols) {
+    if (!d || !d->A || !d->W || !d->C || !scale) return COGS_E_INVALID;
+    CogsGemm g = to_gemm(d);
+    if (q_scale != 0.f) { g.q_scale = q_scale; g.q_cols = q_cols; }
+    return cogs_k_gemm_rows_fp8((hipStream_t)stream, g, scale);
 }
 
 cogs_status cogs_attention_rows(cogs_stream stream, const cogs_attn_rows_desc* d) {

@@ -49,7 +49,8 @@ static char* kv_row(void* base, int l, int max_len, int row, size_t row_bytes) {
 }
 
 // ---- one decoder layer, written once. Its callers differ in LayerArgs and in two callables:
-//   linear(g, codes, scales)   launches the GEMM of one linear: cogs_k_gemm, the e4m3 GEMV on (codes, scales), or cogs_k_gemm_rows
+//   linear(g, codes, scales)   launches the GEMM of one linear: cogs_k_gemm, the e4m3 GEMV on (codes, scales), cogs_k_gemm_rows, or
+//                              cogs_k_gemm_rows_fp8 on (codes, scales)
 //   attend(l)                  everything between the QKV GEMM and the out-projection: puts the new K / V rows where they
 //                              belong and runs the attention from b.qkv into b.att
 struct LayerArgs {
@@ -347,15 +348,22 @@ cogs_status cogs_llm_decode_rows_slots(cogs_handle h, cogs_stream stream, const 
     const AttnTuning tune = cogs_k_attention_tuning();
     const LlmScratch b = rows_scratch(w, R, kv->prefix_len, tune, ws);
     if (!ws || ws_bytes < b.bytes) return COGS_E_WORKSPACE;
-    // the e4m3 codes serve single-row steps only: this step reads the (dequantised) matrices of cogs_llm_weights
+    // llm_last_decode_fp8 speaks of single-token cogs_llm_forward steps only. With e4m3 codes attached and llm_rows_fp8 on, this
+    // step streams the codes through cogs_k_gemm_rows_fp8, else the (dequantised) matrices of cogs_llm_weights: the same bits
     g_cogs_debug.llm_last_decode_fp8 = 0;
+    const bool fp8 = h->fp8_ok && g_cogs_debug.llm_rows_fp8 != 0;
+    g_cogs_debug.llm_last_rows_fp8 = fp8 ? 1 : 0;
     const int tl = kv->tail_len, position = kv->prefix_len + tl;      // lockstep: one position, one rotary row for every row
     if (hipMemcpyAsync(b.x, embeds, (size_t)R * H * es, hipMemcpyDeviceToDevice, st) != hipSuccess) return COGS_E_HIP;
     if (hipMemsetD32Async((hipDeviceptr_t)b.pos, position, R, st) != hipSuccess) return COGS_E_HIP;
     { PROF(COGS_PROF_OTHER); COGS_TRY(cogs_k_llm_rope_table(st, b.rc, nullptr, b.pos, 0, R, h->llm_inv_freq, hd / 2)); }
     const int nsplit = cogs_attn_rows_nsplit(kv->prefix_len, tune);
     const size_t tail_row = (size_t)kv->tail_max * kvd;               // elements between two rows' tails
-    auto linear = [&](CogsGemm& g, const uint8_t*, const float*) -> int { return cogs_k_gemm_rows(st, g); };
+    auto linear = [&](CogsGemm& g, const uint8_t* codes, const float* scales) -> int {
+        if (!fp8) return cogs_k_gemm_rows(st, g);
+        g.W = codes; g.ldw = g.K;
+        return cogs_k_gemm_rows_fp8(st, g, scales);
+    };
     // K / V: every row's new K / V goes behind its own tail; the attention reads the shared prefix and the row's tail
     auto attend = [&](int l) -> int {
         char* tk = (char*)kv->tail_k + (size_t)l * R * tail_row * es;
@@ -376,11 +384,13 @@ cogs_status cogs_llm_decode_rows_slots(cogs_handle h, cogs_stream stream, const 
         PROF(COGS_PROF_ATTN);
         return cogs_k_attention_rows(st, a);
     };
-    const LayerArgs a{R, b.x, false, true, nullptr, nullptr, cogs_llm_fp8_layer{}};
-    for (int l = 0; l < w.layers; ++l) COGS_TRY(llm_layer(h, st, l, b, a, linear, attend));
+    for (int l = 0; l < w.layers; ++l) {
+        const LayerArgs a{R, b.x, false, true, nullptr, nullptr, fp8 ? h->fp8_layers[l] : cogs_llm_fp8_layer{}};
+        COGS_TRY(llm_layer(h, st, l, b, a, linear, attend));
+    }
     { PROF(COGS_PROF_NORM); COGS_TRY(cogs_k_rmsnorm(st, dt, b.x, b.ln, w.final_norm, R, H, w.rms_eps)); }
     CogsGemm g = lm_head_gemm(w, b.ln, R, logits, w.vocab, 0, w.vocab);
-    { PROF(COGS_PROF_GEMM); COGS_TRY(cogs_k_gemm_rows(st, g)); }
+    { PROF(COGS_PROF_GEMM); COGS_TRY(linear(g, h->fp8.lm_head_q, h->fp8.lm_head_s)); }
     kv->tail_len = tl + 1;
     return COGS_OK;
 }

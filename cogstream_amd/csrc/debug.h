@@ -49,6 +49,7 @@
     X(vit_split_max, 1099511627776LL, "clips above this many patches are encoded on one stream")                           \
     X(llm_split_keys, 0, "> 0: keys per split of the decode attention (0: chosen from the context)")                        \
     X(llm_decode_fp8, 1, "cogs_llm_forward with e4m3 weights attached (cogs_llm_attach_fp8): 1 single-token steps read them, 0 the dequantised bf16 / fp32 copy (the in-process A/B)") \
+    X(llm_rows_fp8, 1, "cogs_llm_decode_rows / _slots with e4m3 weights attached: 1 the multi-row step streams the codes (cogs_gemm_rows_fp8; measured faster at every R), 0 the dequantised bf16 copy (the in-process A/B; the same bits either way)") \
     X(beam_gather_tails, 0, "tests: 1 = beam search (llm.py, read through cogs_debug_get) copies every beam's tail behind its parent's per step and passes no slot table; 0 the tails stay where they were written and cogs_attention_rows reads them through the table") \
     X(km_row_groups, 0, "> 0: row groups of the k-means distance pass (0: sized to fill the chip)")                       \
     /* ---- teacher-forced scoring (csrc/lm_score.hip) ---- */                                                              \
@@ -77,6 +78,8 @@ struct CogsDebug {
     std::atomic<long long> lm_score_last_cols{0};
     // ... and whether the last cogs_llm_forward / _segments took the e4m3 GEMVs (1) or the weights' own dtype (0)
     std::atomic<long long> llm_last_decode_fp8{0};
+    // ... and whether the last cogs_llm_decode_rows / _slots streamed the e4m3 codes (1) or the (dequantised) bf16 matrices (0)
+    std::atomic<long long> llm_last_rows_fp8{0};
     // ... and which path the last cogs_sample took: 0 none yet, 1 slice top-k + merge (0 < top_k <= 64), 2 whole-row
     std::atomic<long long> sample_last_path{0};
 };

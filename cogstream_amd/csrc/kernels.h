@@ -107,6 +107,9 @@ int cogs_k_attention_combine(hipStream_t st, const AttnPlan& plan, const float* 
 int cogs_k_attention_rows(hipStream_t st, const CogsAttnRows& a);     // both of the above
 // gemm_rows.hip: bf16, 1 <= M <= 16, weights streamed once as the MFMA operand (not reachable through cogs_k_gemm: its plan is pinned)
 int cogs_k_gemm_rows(hipStream_t st, const CogsGemm& g);
+// the same with W = OCP e4m3fn codes [N][ldw bytes] and one power-of-two fp32 scale per row (ldw % 16 == 0): the bits of
+// cogs_k_gemm_rows on the dequantised matrix code * scale
+int cogs_k_gemm_rows_fp8(hipStream_t st, const CogsGemm& g, const float* scale);
 long cogs_k_gemm_launch_count();   // kernels launched by cogs_k_gemm so far in this process
 
 

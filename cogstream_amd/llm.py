@@ -105,7 +105,10 @@ class Qwen2Engine:
     def __init__(self, state: Dict[str, torch.Tensor], cfg: LlmConfig, dtype=torch.bfloat16, device="cuda",
                  decode_weights: Optional[str] = None):
         """decode_weights="fp8": W8A16 decode -- single-token steps stream e4m3 codes of the linears (half the bytes), every
-        other pass reads the dequantised weights through the usual kernels (weights.PackedLlm / fp8_model_state)"""
+        other pass reads the dequantised weights through the usual kernels (weights.PackedLlm / fp8_model_state). The
+        multi-row step behind num_return_sequences / num_beams (decode_rows) streams the codes too (cogs_gemm_rows_fp8);
+        the debug switch llm_rows_fp8 = 0 sends it through the dequantised weights again, with the same logits bits
+        """
         self.cfg, self.dtype, self.device = cfg, dtype, torch.device(device)
         self.handle = get_handle(self.device)
         self.packed = PackedLlm(state, cfg, dtype, self.device, decode_weights=decode_weights)

@@ -103,6 +103,37 @@ def gemm_rows(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = N
     return out
 
 
+def gemm_rows_fp8(a: torch.Tensor, codes: torch.Tensor, scale: torch.Tensor, bias: Optional[torch.Tensor] = None, *,
+                  act: int = L.ACT_NONE, residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                  out_f32: bool = False, rope_cos: Optional[torch.Tensor] = None, rope_sin: Optional[torch.Tensor] = None,
+                  rope_cols: int = 0, head_dim: int = 0, q_scale: float = 0.0, q_cols: int = 0,
+                  row_stats: Optional[torch.Tensor] = None, ln_ab: Optional[torch.Tensor] = None,
+                  col_c: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[M,N] = epilogue(scale[n] * (a[M,K] @ e4m3(codes[N,K])^T)) for 1 <= M <= 16 bf16 rows (cogs_gemm_rows_fp8 in
+    include/cogs.h): gemm_rows on the codes and scales quantize_fp8_rows makes, bit-identical to gemm_rows on the dequantised
+    matrix. scale None is passed on as NULL; row_stats / ln_ab / col_c exist to be refused (COGS_E_UNSUPPORTED)."""
+    _need_cuda(a, codes, scale, bias, residual, out, rope_cos, rope_sin, row_stats, ln_ab, col_c)
+    M, K = a.shape
+    N = codes.shape[0]
+    assert codes.dtype == torch.uint8 and codes.shape[1] == K and a.stride(1) == 1 and codes.stride(1) == 1
+    assert scale is None or (scale.dtype == torch.float32 and scale.is_contiguous() and scale.numel() == N)
+    if out is None:
+        out = torch.empty(M, N // 2 if act == L.ACT_SWIGLU else N, device=a.device, dtype=torch.float32 if out_f32 else a.dtype)
+    d = L.GemmDesc()
+    d.dtype = dtype_code(a.dtype)
+    d.A, d.lda = ptr(a), a.stride(0)
+    d.W, d.ldw = ptr(codes), codes.stride(0)
+    d.C, d.ldc = ptr(out), out.stride(0)
+    d.bias = ptr(bias)
+    d.residual, d.ldr = ptr(residual), (residual.stride(0) if residual is not None else 0)
+    d.M, d.N, d.K = M, N, K
+    d.act, d.out_f32 = act, int(out_f32)
+    d.rope_cos, d.rope_sin, d.rope_cols, d.head_dim = ptr(rope_cos), ptr(rope_sin), rope_cols, head_dim
+    d.row_stats, d.ln_ab, d.col_c = ptr(row_stats), ptr(ln_ab), ptr(col_c)
+    check(L.lib.cogs_gemm_rows_fp8(current_stream(), C.byref(d), ptr(scale), q_scale, q_cols), "cogs_gemm_rows_fp8")
+    return out
+
+
 def attention_rows(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, tail_k: torch.Tensor, tail_v: torch.Tensor, *,
                    prefix_len: int, tail_len: int, hq: int, hkv: int, head_dim: int = 128, nsplit: int = 1,
                    out: Optional[torch.Tensor] = None, tail_slot: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -94,7 +94,7 @@ const char* cogs_debug_list(void);
  * only; every older signature and structure is unchanged). Added since without a new revision string (new entry points
  * and structures only): cogs_gemm_rows, cogs_attention_rows / cogs_attn_rows_desc, cogs_llm_decode_rows /
  * cogs_llm_decode_rows_workspace_bytes / cogs_kv_rows; cogs_attn_rows_desc.tail_slot / tail_slot_ld (appended, 0 = off),
- * cogs_llm_decode_rows_slots, cogs_beam_topk / cogs_beam_topk_workspace_bytes, cogs_sub_rows. */
+ * cogs_llm_decode_rows_slots, cogs_beam_topk / cogs_beam_topk_workspace_bytes, cogs_sub_rows, cogs_gemm_rows_fp8. */
 
 /* C[M,N] = epilogue(A[M,K] . W[N,K]^T). nn.Linear / Conv2d(k=s=14) replacement
  * (model/modeling_videollama3_encoder.py:194-210,246-248,275,369-373; cogreasoner_chat.py:179-211).
@@ -178,6 +178,17 @@ cogs_status cogs_ln_finalize(cogs_stream stream, const float* row_stats, int row
  * COGS_E_UNSUPPORTED, before any launch: dtype != COGS_DT_BF16, M > 16, ln_ab, row_stats, hm_rows, rope_lut, the GELUs.
  * cogs_gemm does not dispatch here: its results for 2 <= M <= 16 stay what they were. */
 cogs_status cogs_gemm_rows(cogs_stream stream, const cogs_gemm_desc* d, float q_scale, int q_cols);
+/* cogs_gemm_rows on e4m3 weights: C[M,N] = epilogue(scale[n] * sum_k A[m,k] * e4m3(W[n][k])). d->W holds OCP e4m3fn codes
+ * [N][ldw] (one byte per weight, ldw in BYTES; 0x7F / 0xFF must not occur), scale one fp32 POWER OF TWO per output column -- what
+ * cogs_quantize_fp8_rows writes; every other field, the shape rules and the epilogues are cogs_gemm_rows's. The codes are the
+ * streamed MFMA operand (half the bytes of the bf16 matrix), converted in registers; forms, k split and order of additions are
+ * those of cogs_gemm_rows, and the scale multiplies the finished fp32 sum once. The result is therefore BIT-IDENTICAL to
+ * cogs_gemm_rows on the dequantised matrix code * scale, wherever the dequantised weights are normal bf16 numbers and the
+ * sums times scale normal fp32 numbers (a subnormal on either side is rounded on one side only).
+ * COGS_E_INVALID: NULL scale, ldw % 16 != 0, ldw < K, W not 16-byte aligned, K % 64 != 0, N % 4 != 0 and what cogs_gemm_rows
+ * rejects for A / C / residual. COGS_E_UNSUPPORTED, before any launch: what cogs_gemm_rows refuses (dtype != COGS_DT_BF16,
+ * M > 16, ln_ab, row_stats, hm_rows, rope_lut, the GELUs). */
+cogs_status cogs_gemm_rows_fp8(cogs_stream stream, const cogs_gemm_desc* d, const float* scale, float q_scale, int q_cols);
 
 /* W8A16 GEMV (single-token decode): C[N] = epilogue(scale[n] * sum_k x[k] * e4m3(W[n][k])). W holds OCP e4m3fn codes (one
  * byte per weight; 0x7F / 0xFF, the NaN codes, must not occur), scale one fp32 POWER OF TWO per output row -- what
@@ -543,11 +554,13 @@ cogs_status cogs_llm_load(cogs_handle h, const cogs_llm_weights* w);
 
 /* e4m3 copies of the packed matrices of the loaded model (cogs_quantize_fp8_rows layout: codes [N][K] dense, scale [N]), in
  * the packing of cogs_llm_layer. While attached, a cogs_llm_forward / _segments over ONE token reads them through
- * cogs_gemv_fp8 instead of the matrices of cogs_llm_weights; every M > 1 GEMM and cogs_lm_score keep reading the latter,
+ * cogs_gemv_fp8 instead of the matrices of cogs_llm_weights, and cogs_llm_decode_rows / _slots reads them through
+ * cogs_gemm_rows_fp8; every other M > 1 GEMM and cogs_lm_score keep reading the latter,
  * which the caller has replaced by the dequantised values so that both evaluate one model. NULL detaches; cogs_llm_load
  * detaches too (the codes belong to one weight set). Needs hidden, inter and heads * head_dim to be multiples of 16.
- * Debug switch llm_decode_fp8 = 0: single-token steps go through the dequantised matrices again (in-process A/B);
- * cogs_debug_get("llm_last_decode_fp8") says what the last forward took. */
+ * Debug switches llm_decode_fp8 = 0 / llm_rows_fp8 = 0: single-token steps / the multi-row step go through the dequantised
+ * matrices again (in-process A/B; the multi-row step gives the same bits either way);
+ * cogs_debug_get("llm_last_decode_fp8") says what the last forward took, "llm_last_rows_fp8" what the last multi-row step. */
 typedef struct {
     const uint8_t *qkv_q, *o_q, *gu_q, *down_q;
     const float *qkv_s, *o_s, *gu_s, *down_s;
@@ -592,8 +605,11 @@ cogs_status cogs_llm_decode_rows_workspace_bytes(cogs_handle h, int R, int max_p
  * (cogs_gemm_rows; bias, rotary at the common position, pre-scaled Q), the new K / V rows into the tails, cogs_attention_rows,
  * o + residual, RMSNorm, gate / up SwiGLU, down + residual; then the final norm and the lm_head -> logits fp32 [R, vocab].
  * Every weight byte is read once per step. bf16 and head_dim 128 only (else COGS_E_UNSUPPORTED); hidden, inter and
- * heads * head_dim must be multiples of 64. With e4m3 codes attached the step reads the dequantised matrices of
- * cogs_llm_weights; cogs_debug_get("llm_last_decode_fp8") then reports 0. Row r's logits do not depend on the other rows. */
+ * heads * head_dim must be multiples of 64. With e4m3 codes attached (cogs_llm_attach_fp8) every GEMM of the step streams
+ * the codes (cogs_gemm_rows_fp8: half the weight bytes, bit-identical logits); with the debug switch llm_rows_fp8 set to 0 it
+ * reads the dequantised matrices of cogs_llm_weights. cogs_debug_get("llm_last_rows_fp8") says which;
+ * "llm_last_decode_fp8" describes single-token cogs_llm_forward steps only and reads 0 after this call either way.
+ * Row r's logits do not depend on the other rows. */
 cogs_status cogs_llm_decode_rows(cogs_handle h, cogs_stream stream, const void* embeds, int R, cogs_kv_rows* kv,
                                  float* logits, void* ws, size_t ws_bytes);
 /* The same step for beam search, where row r continues the sequence row parent[r] held one step ago: tail_slot (device int32
