@@ -134,6 +134,14 @@ class GemvFp8Desc(C.Structure):
     ]
 
 
+class GemmFusedArgs(C.Structure):
+    _fields_ = [
+        ("q_scale", c_float), ("q_cols", c_int),
+        ("rms_gamma", c_void_p), ("rms_eps", c_float),
+        ("kv_k", c_void_p), ("kv_v", c_void_p), ("kv_col0", c_int), ("kv_dim", c_int),
+    ]
+
+
 class LlmFp8Layer(C.Structure):
     _fields_ = [(n, c_void_p) for n in ("qkv_q", "o_q", "gu_q", "down_q", "qkv_s", "o_s", "gu_s", "down_s")]
 
@@ -180,6 +188,7 @@ SIGNATURES = {
     "cogs_gemm": (c_int, [c_void_p, C.POINTER(GemmDesc)]),
     "cogs_gemm_rows": (c_int, [c_void_p, C.POINTER(GemmDesc), c_float, c_int]),
     "cogs_gemm_rows_fp8": (c_int, [c_void_p, C.POINTER(GemmDesc), c_void_p, c_float, c_int]),
+    "cogs_gemm_fused": (c_int, [c_void_p, C.POINTER(GemmDesc), C.POINTER(GemmFusedArgs)]),
     "cogs_attention_rows": (c_int, [c_void_p, C.POINTER(AttnRowsDesc)]),
     "cogs_llm_decode_rows_workspace_bytes": (c_int, [c_void_p, c_int, c_int, C.POINTER(c_size_t)]),
     "cogs_llm_decode_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int, C.POINTER(KVRows), c_void_p, c_void_p, c_size_t]),

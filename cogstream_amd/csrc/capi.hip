@@ -213,6 +213,16 @@ cogs_status cogs_gemm_rows_fp8(cogs_stream stream, const cogs_gemm_desc* d, cons
     return cogs_k_gemm_rows_fp8((hipStream_t)stream, g, scale);
 }
 
+cogs_status cogs_gemm_fused(cogs_stream stream, const cogs_gemm_desc* d, const cogs_gemm_fused_args* a) {
+    if (!d || !a || !d->A || !d->W || !d->C) return COGS_E_INVALID;
+    if (d->ln_ab && d->bias) return COGS_E_INVALID;     // as cogs_gemm
+    CogsGemm g = to_gemm(d);
+    if (a->q_scale != 0.f) { g.q_scale = a->q_scale; g.q_cols = a->q_cols; }
+    g.rms_gamma = a->rms_gamma; g.rms_eps = a->rms_eps;
+    g.kv_k = a->kv_k; g.kv_v = a->kv_v; g.kv_col0 = a->kv_col0; g.kv_dim = a->kv_dim;
+    return cogs_k_gemm((hipStream_t)stream, g);
+}
+
 cogs_status cogs_attention_rows(cogs_stream stream, const cogs_attn_rows_desc* d) {
     if (!d || !d->Q || !d->K || !d->V || !d->tail_k || !d->tail_v || !d->O) return COGS_E_INVALID;
     if (d->dtype != COGS_DT_BF16) return COGS_E_UNSUPPORTED;

@@ -1042,7 +1042,7 @@ int cogs_k_gemm(hipStream_t st, const CogsGemm& g) {
     if (g.hm_rows > 0 && (g.M == 1 || g.dtype != COGS_DT_BF16)) return COGS_E_UNSUPPORTED;       // head-major output: bf16 MFMA kernels only
     EpiArgs epi;
     if (g.M > 1) {
-        if (g.rms_gamma) return COGS_E_UNSUPPORTED;   // fused RMSNorm exists for the single-token GEMV only
+        if (g.rms_gamma || g.kv_k) return COGS_E_UNSUPPORTED;   // fused RMSNorm and the K / V row redirect exist for the single-token GEMV only
         const int rc = cogs_fill_epi(g, &epi);
         if (rc != COGS_OK) return rc;
     }

@@ -364,7 +364,9 @@ int cogs_k_gemv(hipStream_t st, const CogsGemm& g) {
     p.N = g.N; p.K = g.K;
     p.rms_gamma = g.rms_gamma; p.rms_eps = g.rms_eps;
     p.kv_k = (char*)g.kv_k; p.kv_v = (char*)g.kv_v; p.kv_col0 = g.kv_col0; p.kv_dim = g.kv_dim;
-    if (g.kv_k && (g.kv_col0 % 4 || g.kv_dim % 4 || g.out_f32 || g.act == COGS_ACT_SWIGLU)) return COGS_E_INVALID;
+    // the K / V regions are the tail of the row: columns behind them would be stored past kv_v + kv_dim
+    if (g.kv_k && (!g.kv_v || g.kv_col0 < 0 || g.kv_dim < 0 || g.kv_col0 % 4 || g.kv_dim % 4 || g.out_f32 || g.act == COGS_ACT_SWIGLU ||
+                   g.kv_col0 + 2 * g.kv_dim != g.N)) return COGS_E_INVALID;
     // 4 rows per wave when that still gives every CU several workgroups, else 2 (N % 4 == 0 keeps pairs whole)
     const bool small_n = g.N / 16 < (int)g_cogs_debug.gemv_small_n;
     const bool dot2 = g_cogs_debug.gemv_dot2 != 0;

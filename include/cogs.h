@@ -94,7 +94,8 @@ const char* cogs_debug_list(void);
  * only; every older signature and structure is unchanged). Added since without a new revision string (new entry points
  * and structures only): cogs_gemm_rows, cogs_attention_rows / cogs_attn_rows_desc, cogs_llm_decode_rows /
  * cogs_llm_decode_rows_workspace_bytes / cogs_kv_rows; cogs_attn_rows_desc.tail_slot / tail_slot_ld (appended, 0 = off),
- * cogs_llm_decode_rows_slots, cogs_beam_topk / cogs_beam_topk_workspace_bytes, cogs_sub_rows, cogs_gemm_rows_fp8. */
+ * cogs_llm_decode_rows_slots, cogs_beam_topk / cogs_beam_topk_workspace_bytes, cogs_sub_rows, cogs_gemm_rows_fp8,
+ * cogs_gemm_fused / cogs_gemm_fused_args. */
 
 /* C[M,N] = epilogue(A[M,K] . W[N,K]^T). nn.Linear / Conv2d(k=s=14) replacement
  * (model/modeling_videollama3_encoder.py:194-210,246-248,275,369-373; cogreasoner_chat.py:179-211).
@@ -189,6 +190,26 @@ cogs_status cogs_gemm_rows(cogs_stream stream, const cogs_gemm_desc* d, float q_
  * rejects for A / C / residual. COGS_E_UNSUPPORTED, before any launch: what cogs_gemm_rows refuses (dtype != COGS_DT_BF16,
  * M > 16, ln_ab, row_stats, hm_rows, rope_lut, the GELUs). */
 cogs_status cogs_gemm_rows_fp8(cogs_stream stream, const cogs_gemm_desc* d, const float* scale, float q_scale, int q_cols);
+
+/* cogs_gemm with the fused pieces the Qwen2 layer adds around its linears (what cogs_llm_forward passes to the same
+ * dispatcher): C[M,N] = epilogue(A[M,K] . W[N,K]^T) with cogs_gemm's descriptor, shape rules and choice of kernel, plus
+ *   q_scale (0 or 1 = off): columns < q_cols are multiplied by it after bias / rotary, before the activation and the one
+ *     rounding (any M; rotary epilogues only: rope_cos != NULL, q_cols % 4 == 0, q_cols <= rope_cols);
+ *   rms_gamma != NULL (M == 1): A is replaced by Qwen2RMSNorm(A) = gamma * (A * rsqrt(mean(A^2) + rms_eps)) on the fly, with
+ *     the roundings of cogs_rmsnorm (gamma [K] in `dtype`, 16-byte aligned);
+ *   kv_k != NULL (M == 1): columns [kv_col0, kv_col0 + kv_dim) are written to kv_k[0..kv_dim) and the next kv_dim columns
+ *     to kv_v[0..kv_dim) instead of C, in `dtype` (kv_col0 + 2 * kv_dim == N; those columns of C are not written).
+ * M == 1 runs the weight-streaming GEMV (the bf16 / fp32 counterpart of cogs_gemv_fp8), M > 1 the planned body.
+ * COGS_E_INVALID: a NULL d / args / A / W / C and what cogs_gemm rejects; q_scale without rope_cos, q_cols % 4 != 0 or q_cols >
+ * rope_cols; with kv_k: a NULL kv_v, kv_col0 or kv_dim negative or not a multiple of 4, kv_col0 + 2 * kv_dim != N, out_f32,
+ * COGS_ACT_SWIGLU. COGS_E_UNSUPPORTED, before any launch: rms_gamma or kv_k with M > 1 (the MFMA bodies know neither), and
+ * what cogs_gemm refuses. A zero-initialised cogs_gemm_fused_args makes the call cogs_gemm. */
+typedef struct {
+    float q_scale; int q_cols;
+    const void* rms_gamma; float rms_eps;
+    void* kv_k; void* kv_v; int kv_col0; int kv_dim;
+} cogs_gemm_fused_args;
+cogs_status cogs_gemm_fused(cogs_stream stream, const cogs_gemm_desc* d, const cogs_gemm_fused_args* args);
 
 /* W8A16 GEMV (single-token decode): C[N] = epilogue(scale[n] * sum_k x[k] * e4m3(W[n][k])). W holds OCP e4m3fn codes (one
  * byte per weight; 0x7F / 0xFF, the NaN codes, must not occur), scale one fp32 POWER OF TWO per output row -- what

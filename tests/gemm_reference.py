@@ -6,6 +6,8 @@ the epilogue is applied in fp64 in the order of csrc/gemm_epilogue.h:
     y = acc                       acc[m][n] = sum_k A[m][k] W[n][k]
     y = rstd[m] * y + col_c[n]    (LN fold; replaces the bias)        or   y = y + bias[n]
     y = rotary(y)                 pair (2i, 2i+1) of a head: (y0 c - y1 s, y1 c + y0 s), (c, s) of row m and pair i
+    y = q * y                     columns < q_cols only (the Q heads, pre-scaled for the attention kernels); q is the fp32
+                                  value the kernel multiplies by
     y = act(y)                    GELU (tanh / erf), or SwiGLU  out[j] = silu(y[2j]) * y[2j+1]
     y = y + R[m][n]
     store (one rounding to the output type)
@@ -20,6 +22,8 @@ on |y_fp32 - y_fp64| carried through the steps:
   * LN fold (one fma): E = rstd E_acc + 2u (|rstd acc| + |col_c|).  Bias (one add): E = E_acc + u |y|.
   * rotary mixes the two columns of a pair with the row's factors: E'_0 = |c| E_0 + |s| E_1 + 2u (|y_0 c| + |y_1 s|),
     and the same for the second column with the roles swapped.
+  * q_scale (one fp32 multiply by the fp32 constant q, columns < q_cols): E = |q| E + u |q y|; a power of two is an
+    exact multiply and adds nothing.
   * activations: the local slope bounds how E grows (GELU: |gelu'| <= 1.13; SiLU: |silu'| <= 1.1), plus the error of
     the device formulas themselves (x * sigmoid(.) through v_exp_f32 / v_rcp_f32 and erff: a few fp32 ulps, and the
     relative error of 2^t grows with |t|): 2^-16 |y_out| + 2^-20 |y_in|.
@@ -67,11 +71,11 @@ def product_and_bound(a: torch.Tensor, w: torch.Tensor):
 
 def epilogue(acc: torch.Tensor, bound: torch.Tensor, *, cols: Optional[torch.Tensor] = None,
              bias: Optional[torch.Tensor] = None, rstd: Optional[torch.Tensor] = None,
-             col_c: Optional[torch.Tensor] = None, rope: Optional[Rope] = None, act: int = ACT_NONE,
-             residual: Optional[torch.Tensor] = None, out_f32: bool = False, out_dtype=torch.bfloat16):
+             col_c: Optional[torch.Tensor] = None, rope: Optional[Rope] = None, q_scale: Optional[float] = None,
+             q_cols: int = 0, act: int = ACT_NONE, residual: Optional[torch.Tensor] = None, out_f32: bool = False, out_dtype=torch.bfloat16):
     """fp64 (reference, tolerance) of the output columns `cols` (all when None) from acc / bound [rows, len(cols)].
     bias / col_c are full [N] vectors (indexed by cols), rstd [rows], residual [rows, len(cols)]; rotary and SwiGLU need
-    whole aligned pairs among the selected columns. SwiGLU returns [rows, len(cols) / 2]."""
+    whole aligned pairs among the selected columns. q_scale: the fp32 factor of the columns < q_cols (None / q_cols 0: off). SwiGLU returns [rows, len(cols) / 2]."""
     dev = acc.device
     N_sel = acc.shape[1]
     if cols is None:
@@ -98,6 +102,12 @@ def epilogue(acc: torch.Tensor, bound: torch.Tensor, *, cols: Optional[torch.Ten
         y, e = y.clone(), e.clone()
         y[:, 0::2], y[:, 1::2] = torch.where(on, r0, y0), torch.where(on, r1, y1)
         e[:, 0::2], e[:, 1::2] = torch.where(on, f0, e0), torch.where(on, f1, e1)
+    if q_scale is not None and q_cols > 0:
+        q = float(torch.tensor(q_scale, dtype=torch.float32))                # the fp32 value, widened
+        on = (cols < q_cols)[None, :]
+        exact = math.frexp(abs(q))[0] == 0.5                                 # a power of two: the multiply rounds nothing
+        e = torch.where(on, abs(q) * e + (0.0 if exact else U32) * (q * y).abs(), e)
+        y = torch.where(on, q * y, y)
     if act == ACT_GELU_TANH or act == ACT_GELU_ERF:
         x = y
         if act == ACT_GELU_TANH:

@@ -23,6 +23,54 @@ def test_library_exports_every_declared_symbol():
     assert b"gfx950" in L.lib.cogs_version()
 
 
+def _struct_fields(hdr, name):
+    """member names of `typedef struct { ... } name;` in declaration order (comments stripped)"""
+    body = re.search(r"typedef struct \{((?:(?!typedef struct).)*?)\}\s*" + name + r"\s*;", hdr, re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    return [re.search(r"([A-Za-z_]\w*)\s*(?:\[[^\]]*\])?\s*$", m.strip()).group(1)
+            for decl in body.split(";") if decl.strip() for m in decl.split(",")]
+
+
+def test_gemm_fused_is_declared_exported_and_bound(tmp_path):
+    """cogs_gemm_fused / cogs_gemm_fused_args: the header's signature and member order are what the binding passes,
+    cogs_gemm_desc keeps its layout, a C compiler lays both structs out as ctypes does, and the entry refuses missing
+    arguments before touching a device"""
+    import ctypes as C
+    import shutil
+    import subprocess
+    from cogstream_amd import _lib as L
+    hdr = open(os.path.join(ROOT, "include", "cogs.h")).read()
+    m = re.search(r"cogs_status\s+cogs_gemm_fused\s*\(([^)]*)\)\s*;", hdr)
+    assert m, "include/cogs.h does not declare cogs_gemm_fused"
+    args = [re.sub(r"\s+", " ", a.strip()) for a in m.group(1).split(",")]
+    assert args == ["cogs_stream stream", "const cogs_gemm_desc* d", "const cogs_gemm_fused_args* args"]
+    res, argtypes = L.SIGNATURES["cogs_gemm_fused"]
+    assert res is C.c_int and argtypes == [C.c_void_p, C.POINTER(L.GemmDesc), C.POINTER(L.GemmFusedArgs)]
+    assert L.lib.cogs_gemm_fused.argtypes == argtypes
+    assert _struct_fields(hdr, "cogs_gemm_fused_args") == [n for n, _ in L.GemmFusedArgs._fields_]
+    assert _struct_fields(hdr, "cogs_gemm_fused_args") == ["q_scale", "q_cols", "rms_gamma", "rms_eps", "kv_k", "kv_v", "kv_col0", "kv_dim"]
+    assert _struct_fields(hdr, "cogs_gemm_desc") == [n for n, _ in L.GemmDesc._fields_]
+    assert _struct_fields(hdr, "cogs_gemm_desc")[-2:] == ["hm_rows", "hm_cols"] and C.sizeof(L.GemmDesc) == 192
+    assert L.SIGNATURES["cogs_gemm"][1] == [C.c_void_p, C.POINTER(L.GemmDesc)]
+    assert " 0.4 " in L.lib.cogs_version().decode()
+    d, f = L.GemmDesc(), L.GemmFusedArgs()
+    assert L.lib.cogs_gemm_fused(None, None, None) == L.E_INVALID
+    assert L.lib.cogs_gemm_fused(None, C.byref(d), None) == L.E_INVALID
+    assert L.lib.cogs_gemm_fused(None, None, C.byref(f)) == L.E_INVALID
+    assert L.lib.cogs_gemm_fused(None, C.byref(d), C.byref(f)) == L.E_INVALID          # no operands
+    if shutil.which("gcc") is not None:
+        src = tmp_path / "s.c"
+        src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "cogs.h"\nint main(void) { printf("%zu %zu %zu %zu %zu\\n", '
+                       'sizeof(cogs_gemm_desc), sizeof(cogs_gemm_fused_args), offsetof(cogs_gemm_fused_args, rms_gamma), '
+                       'offsetof(cogs_gemm_fused_args, kv_k), offsetof(cogs_gemm_fused_args, kv_col0)); return 0; }\n')
+        exe = tmp_path / "s"
+        r = subprocess.run(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr
+        got = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True).stdout.split()]
+        F = L.GemmFusedArgs
+        assert got == [C.sizeof(L.GemmDesc), C.sizeof(F), F.rms_gamma.offset, F.kv_k.offset, F.kv_col0.offset], got
+
+
 def test_header_is_plain_c(tmp_path):
     """include/cogs.h is the boundary a C caller binds: it must compile as C99 on its own, every entry point a
     file-scope declaration (a function declared inside a struct body is C++ only and hides the symbol from C)"""

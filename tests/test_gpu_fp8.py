@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import gemm_reference as R
+import gemv_reference as G
 from conftest import rel_err
 from test_fp8_host import _formula_table, _inputs
 
@@ -100,25 +101,15 @@ def _quantised(dev, N, K, dtype, seed):
     return codes, scale, deq, g
 
 
-def _rmsnorm_rows(x, gamma, eps, rel):
-    """Qwen2RMSNorm of the single row x in the kernel's arithmetic (csrc/norm.hip): rstd in fp32 from the fp64 mean square,
-    times (1 + rel); bf16: weight * (x * rstd).to(bf16), rounded to bf16 again; fp32: weight * (x * rstd)"""
-    rstd = (1.0 / torch.sqrt(x.double().pow(2).mean() + eps) * (1.0 + rel)).float()
-    n = x.float() * rstd
-    if x.dtype == BF16:
-        n = n.to(BF16).float()
-    n = gamma.float() * n
-    return n.to(x.dtype)
-
-
 def run_cell(dev, N, K, *, dtype=BF16, bias=False, res=None, act=R.ACT_NONE, out_f32=False, rope=None, rope_cols=0,
-             q_cols=0, kv_dim=0, rms=False, seed=1, **sw):
+             q_cols=0, q_scale=0.125, kv_dim=0, rms=False, low=False, seed=1, **sw):
     """one cogs_gemv_fp8 through the C ABI; every output element against its own fp64 band, guards bit for bit.
-    res: None | "sep" | "inplace"; rope: None | "inter" | "sep"; q_cols > 0: q_scale = 2^-3 on the columns below it;
-    kv_dim > 0: the last 2 * kv_dim columns are the new K / V cache row"""
+    res: None | "sep" | "inplace"; rope: None | "inter" | "sep"; q_cols > 0: q_scale on the columns below it;
+    kv_dim > 0: the last 2 * kv_dim columns are the new K / V cache row; low: x at 2e-3 of the ordinary magnitude, where
+    the mean square is of the order of rms_eps (tests/test_gemv_reference.py)"""
     L = _L()
     codes, scale, deq, g = _quantised(dev, N, K, dtype, seed)
-    x = (torch.randn(K, generator=g, device=dev) * 0.7 + 0.1).to(dtype)
+    x = ((torch.randn(K, generator=g, device=dev) * 0.7 + 0.1) * (2e-3 if low else 1.0)).to(dtype)
     swiglu = act == R.ACT_SWIGLU
     ocols = N // 2 if swiglu else N
     odt = F32 if (out_f32 or dtype == F32) else dtype
@@ -132,16 +123,7 @@ def run_cell(dev, N, K, *, dtype=BF16, bias=False, res=None, act=R.ACT_NONE, out
         eps = 1e-6
         gamma = (1 + 0.1 * torch.randn(K, generator=g, device=dev)).to(dtype)
         d.rms_gamma, d.rms_eps = gamma.data_ptr(), eps
-        a = _rmsnorm_rows(x, gamma, eps, 0.0).view(1, K)
-        # The device's rstd is an fp32 computation: every lane adds its K / 64 squares in sequence, six butterfly levels join
-        # the lanes, then a division, the eps addition and v_rsq_f32 (1 ulp). Worst case, relative to the exact rstd:
-        # half of (K / 64 + 9) roundings of 2^-24 on the sum, plus 2^-23 + 2^-24. That scales a (fp32), or moves an element by
-        # a bf16 step where x * rstd lies that close to a rounding boundary (bf16; the rounding is monotonic in rstd, so the
-        # two ends of the interval decide). What the ends change enters the tolerance through |W|: nothing when no element
-        # is near a boundary.
-        rel = 0.5 * (K / 64 + 9) * 2.0 ** -24 + 2.0 ** -23 + 2.0 ** -24
-        lo, hi = _rmsnorm_rows(x, gamma, eps, -rel), _rmsnorm_rows(x, gamma, eps, rel)
-        extra = ((hi.double() - lo.double()).abs().view(1, K) @ deq.double().abs().t())
+        a, extra = G.rms_operand(x, gamma, eps, deq)        # the rstd band: tests/gemv_reference.py
     acc, bound = R.product_and_bound(a, deq)
     if extra is not None:
         bound = bound + extra
@@ -164,15 +146,8 @@ def run_cell(dev, N, K, *, dtype=BF16, bias=False, res=None, act=R.ACT_NONE, out
             keep.append(tc)
         d.rope_cols, d.head_dim = rope_cols, HD
         rope_r = R.Rope(cos.double(), sin.double(), rope_cols, HD)
-    bias_ref = bias_t
     if q_cols:
-        # tests/gemm_reference.py has no q_scale step. With a power of two the step commutes exactly with every rounding
-        # around it, so the reference runs on pre-scaled columns: q * rope(acc + bias) = rope(q * acc + q * bias)
-        qs = 0.125
-        d.q_scale, d.q_cols = qs, q_cols
-        colscale = torch.where(torch.arange(N, device=dev) < q_cols, qs, 1.0).double()
-        acc, bound = acc * colscale[None, :], bound * colscale[None, :]
-        bias_ref = bias_t.double() * colscale if bias_t is not None else None
+        d.q_scale, d.q_cols = q_scale, q_cols
     cbuf = _filled(64 + ocols + 64, odt, dev)
     cview = cbuf[64:64 + ocols]
     d.C = cview.data_ptr()
@@ -197,7 +172,7 @@ def run_cell(dev, N, K, *, dtype=BF16, bias=False, res=None, act=R.ACT_NONE, out
         kv_guard = _bits(kvbuf)[~kv_inside].clone()
         inside[64 + N - 2 * kv_dim:64 + N] = False                          # those columns of C must stay untouched
     guard = _bits(cbuf)[~inside].clone()
-    ref, tol = R.epilogue(acc, bound, bias=bias_ref, rope=rope_r, act=act,
+    ref, tol = R.epilogue(acc, bound, bias=bias_t, rope=rope_r, q_scale=q_scale if q_cols else None, q_cols=q_cols, act=act,
                           residual=res_t.view(1, -1) if res_t is not None else None, out_f32=out_f32, out_dtype=odt)
     with switches(**sw):
         rc = L.lib.cogs_gemv_fp8(L.current_stream(), C.byref(d))
@@ -235,13 +210,14 @@ def test_k_edges(dev, K, dtype):
             run_cell(dev, 264, K, dtype=dtype, bias=True, res="sep", seed=K, gemv_small_n=small_n, **var)
 
 
-@pytest.mark.parametrize("epi", ["qkv", "qkv sep", "res", "res in place", "swiglu", "f32out"])
+@pytest.mark.parametrize("epi", ["qkv", "qkv model scale", "qkv sep", "res", "res in place", "swiglu", "f32out"])
 def test_decode_epilogues_at_the_lm_head_width(dev, epi):
     """what llm_forward_impl asks of the GEMV, at N = 152 064: bias + rotary + q_scale + the K / V row written into the cache
     (1100 + 2 x 44 heads of 128), the residual separate and in place, SwiGLU, fp32 logits"""
     N = 152064
     kvd = 44 * HD
     kw = {"qkv": dict(bias=True, rope="inter", rope_cols=N - kvd, q_cols=N - 2 * kvd, kv_dim=kvd),
+          "qkv model scale": dict(bias=True, rope="inter", rope_cols=N - kvd, q_cols=N - 2 * kvd, q_scale=G.model_q_scale(HD), kv_dim=kvd),
           "qkv sep": dict(bias=True, rope="sep", rope_cols=N - kvd, q_cols=N - 2 * kvd, kv_dim=kvd),
           "res": dict(res="sep"), "res in place": dict(res="inplace"), "swiglu": dict(act=R.ACT_SWIGLU),
           "f32out": dict(out_f32=True)}[epi]
@@ -261,6 +237,8 @@ def test_fused_rmsnorm(dev, K, dtype):
             run_cell(dev, N, K, dtype=dtype, rms=True, bias=True, rope="inter", rope_cols=N - kvd, q_cols=N - 2 * kvd, kv_dim=kvd, seed=K + 1, **sw)
             run_cell(dev, 1032, K, dtype=dtype, rms=True, act=R.ACT_SWIGLU, seed=K + 2, **sw)
             run_cell(dev, 1028, K, dtype=dtype, rms=True, out_f32=True, seed=K + 3, **sw)
+    # the epsilon itself: at the ordinary magnitude an rstd without rms_eps passes every cell above
+    run_cell(dev, 264, K, dtype=dtype, rms=True, low=True, out_f32=True, seed=K + 4, **VARIANTS[0])
 
 
 def test_invalid_descriptors_return_their_status_before_any_launch(dev):

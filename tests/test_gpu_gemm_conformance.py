@@ -18,6 +18,7 @@ import pytest
 import torch
 
 import gemm_reference as R
+import gemv_reference as G
 
 BF16, F32 = torch.bfloat16, torch.float32
 TRACE16, TRACE32 = 0x7F7F, 0x7F7F7F7F        # bf16 3.39e38 / fp32 3.39e38: finite, far outside any result
@@ -47,6 +48,9 @@ REQUIRED = (
        (1, "ldc%8==4"), (2, "ldc%8==4"), (4, "ldc%8==4"), (5, "ldc%8==4"), (6, "ldc%8==4")]
     + [(b, "exact " + e) for b in (1, 2, 4) for e in ("plain", "bias", "res", "bias+res", "f32out", "bias+rope+hm", "rope swap")]
     + [(b, SPECIALISED[m]) for b in (1, 2) for m in SPECIALISED]
+    + [(b, e + q) for b in (1, 2, 4, 5) for e in ("bias+rope", "bias+rope sep_sin", "lnfold+rope", "bias+rope+hm", "lnfold+rope+hm")
+       for q in (" q_scale on a tile boundary", " q_scale straddling a tile")]
+    + [(3, e + q) for e in ("bias+rope lut", "lnfold+rope lut") for q in (" q_scale on a tile boundary", " q_scale straddling a tile")]
     + [(6, e) for e in ("plain", "bias", "res", "bias+rope", "bias+rope sep_sin", "bias+gelu_tanh", "bias+gelu_erf", "swiglu",
                         "f32out", "gemv small_n", "gemv big_n", "gemv dot2=0")]
 )
@@ -146,10 +150,11 @@ def _rope_tables(dev, g, M, hd, form):
 # ----------------------------------------------------------------------------------------------------------- one cell
 def run_cell(dev, body, M, N, K, *, dtype=BF16, bias=False, res=None, act=R.ACT_NONE, out_f32=False, rope=None,
              hd=HD_VIT, rope_cols=None, ln=False, stats=False, hm=False, lda_pad=0, ldc_pad=0, c_off=0, ldr_pad=0,
-             exact=False, seed=1, tags=(), also_wgs0=False, **sw):
+             exact=False, seed=1, tags=(), also_wgs0=False, q_cols=0, **sw):
     """One GEMM through the C ABI with the given epilogue and layout; asserts the body, the values of every output element
     against fp64, the CPU fp64 spot check of a few rows, and the guard bands. res: None | "sep" | "inplace".
-    rope: None | "inter" | "sep" | "lut" | "swap" | "swap_sep". Returns the output [M, N or N/2] (fp32 / bf16)."""
+    rope: None | "inter" | "sep" | "lut" | "swap" | "swap_sep". q_cols > 0: through cogs_gemm_fused, with the model's q_scale for
+    head_dim hd on the columns below it. Returns the output [M, N or N/2] (fp32 / bf16)."""
     L = _L()
     a, w, acc, bound, g = _operands(dev, M, N, K, dtype, exact, seed)
     swiglu = act == R.ACT_SWIGLU
@@ -227,21 +232,31 @@ def run_cell(dev, body, M, N, K, *, dtype=BF16, bias=False, res=None, act=R.ACT_
     if stats:
         sbuf = _filled((M + 8) * (N // 64) * 2, F32, dev)
         d.row_stats = sbuf.data_ptr()
+    q_scale = G.model_q_scale(hd) if q_cols else None
+    fused = L.GemmFusedArgs()
+    if q_cols:
+        fused.q_scale, fused.q_cols = q_scale, q_cols
+
+    def launch():
+        if q_cols:
+            return L.lib.cogs_gemm_fused(L.current_stream(), C.byref(d), C.byref(fused))
+        return L.lib.cogs_gemm(L.current_stream(), C.byref(d))
+
     with switches(**sw):
         L.debug_set("gemm_choice", 0)
-        st = L.lib.cogs_gemm(L.current_stream(), C.byref(d))
+        st = launch()
         got_body = L.debug_get("gemm_last_body")
         torch.cuda.synchronize()
     mask = epi_mask(bias=bias, res=res is not None, rope=rope is not None, act=act, out_f32=out_f32, stats=stats, ln=ln, hm=hm)
     what = (f"body {body} M={M} N={N} K={K} {str(dtype)[6:]} mask {SPECIALISED.get(mask, 'generic')} rope={rope} "
-            f"res={res} lda_pad={lda_pad} ldc_pad={ldc_pad} c_off={c_off} ldr_pad={ldr_pad} {sw}")
+            f"q_cols={q_cols} res={res} lda_pad={lda_pad} ldc_pad={ldc_pad} c_off={c_off} ldr_pad={ldr_pad} {sw}")
     assert st == L.OK, (what, st)
     assert got_body == body, f"{what}: ran body {got_body}"
     out = out_view().clone()
     # values: fp64 reference on the device
     rope_ref = R.Rope(cos, sin, d.rope_cols, hd) if rope is not None else None
-    ref, tol = R.epilogue(acc, bound, bias=bias_t, rstd=rstd, col_c=col_c, rope=rope_ref, act=act, residual=res_t,
-                          out_f32=out_f32, out_dtype=odt)
+    ref, tol = R.epilogue(acc, bound, bias=bias_t, rstd=rstd, col_c=col_c, rope=rope_ref, q_scale=q_scale, q_cols=q_cols, act=act,
+                          residual=res_t, out_f32=out_f32, out_dtype=odt)
     if exact:
         bad = out.double() != ref
         assert not bool(bad.any()), f"{what}: {int(bad.sum())} elements differ from the exact result"
@@ -249,7 +264,7 @@ def run_cell(dev, body, M, N, K, *, dtype=BF16, bias=False, res=None, act=R.ACT_
         R.assert_within(out, ref, tol, what)
     # the yardstick itself: a CPU fp64 recomputation of a few rows on a few aligned column groups
     _cpu_spot_check(out, a, w, rows=sorted({0, M - 1, M // 2, (7 * M) // 9}), N=N, bias=bias_t, rstd=rstd, col_c=col_c,
-                    rope=rope_ref, act=act, residual=res_t, out_f32=out_f32, odt=odt, what=what)
+                    rope=rope_ref, q_scale=q_scale, q_cols=q_cols, act=act, residual=res_t, out_f32=out_f32, odt=odt, what=what)
     # guard bands: nothing outside the output changed
     after = _bits(cbuf)[~inside]
     assert torch.equal(after, guard_before), f"{what}: {int((after != guard_before).sum())} elements written outside C"
@@ -265,7 +280,7 @@ def run_cell(dev, body, M, N, K, *, dtype=BF16, bias=False, res=None, act=R.ACT_
         if res == "inplace":
             cview.copy_(res_t)
         with switches(gemm_wgs=0, **sw):
-            assert L.lib.cogs_gemm(L.current_stream(), C.byref(d)) == L.OK
+            assert launch() == L.OK
             assert L.debug_get("gemm_last_body") == body
         torch.cuda.synchronize()
         assert torch.equal(_bits(cbuf), _bits(cbuf2)), f"{what}: persistent walk != one tile per workgroup"
@@ -275,6 +290,8 @@ def run_cell(dev, body, M, N, K, *, dtype=BF16, bias=False, res=None, act=R.ACT_
         label += " sep_sin"
     if rope == "lut":
         label += " lut"
+    if q_cols:
+        label += " q_scale on a tile boundary" if q_cols % 64 == 0 else " q_scale straddling a tile"
     reached = {label}
     if res == "inplace":
         reached.add(label + " in place")
@@ -291,10 +308,11 @@ def run_cell(dev, body, M, N, K, *, dtype=BF16, bias=False, res=None, act=R.ACT_
     return out
 
 
-def _cpu_spot_check(out, a, w, *, rows, N, bias, rstd, col_c, rope, act, residual, out_f32, odt, what):
+def _cpu_spot_check(out, a, w, *, rows, N, bias, rstd, col_c, rope, act, residual, out_f32, odt, what, q_scale=None, q_cols=0):
     gen = torch.Generator().manual_seed(N)
     groups = sorted({0, N // 4 - 1, (N // 2) // 4, N // 4 - 1 if N >= 8 else 0,
-                     *torch.randint(0, N // 4, (6,), generator=gen).tolist(), *[min(c // 4, N // 4 - 1) for c in (124, 128, 252, 256)]})
+                     *torch.randint(0, N // 4, (6,), generator=gen).tolist(), *[min(c // 4, N // 4 - 1) for c in (124, 128, 252, 256)],
+                     *([min(max(q_cols // 4 + k, 0), N // 4 - 1) for k in (-1, 0)] if q_cols else [])})
     cols = torch.tensor([4 * gi + j for gi in groups for j in range(4)])
     r = torch.tensor(rows)
     ac = a[r].cpu().double()
@@ -307,7 +325,7 @@ def _cpu_spot_check(out, a, w, *, rows, N, bias, rstd, col_c, rope, act, residua
         rope_c = R.Rope(rope.cos[r.to(rope.cos.device)].cpu(), rope.sin[r.to(rope.sin.device)].cpu(), rope.cols, rope.head_dim)
     ref, tol = R.epilogue(acc, bound, cols=cols, bias=None if bias is None else bias.cpu(),
                           rstd=None if rstd is None else rstd[r.to(rstd.device)].cpu(),
-                          col_c=None if col_c is None else col_c.cpu(), rope=rope_c, act=act,
+                          col_c=None if col_c is None else col_c.cpu(), rope=rope_c, q_scale=q_scale, q_cols=q_cols, act=act,
                           residual=None if residual is None else residual[r.to(residual.device)][:, cols.to(residual.device)].cpu(),
                           out_f32=out_f32, out_dtype=odt)
     ocols = cols[0::2] // 2 if act == R.ACT_SWIGLU else cols
@@ -507,6 +525,9 @@ def test_k_tile_body_and_the_rotary_lut(dev):
     run_cell(dev, 3, 1500, 1512, 128, bias=True, rope="lut", hd=HD_VIT, rope_cols=1008, gemm_split=0, gemm_pp64=0)
     run_cell(dev, 3, 2048, 3 * 1152, 128, bias=True, rope="lut", hd=HD_VIT, rope_cols=2304, gemm_split=0, gemm_pp64=0)
     run_cell(dev, 3, 2048, 3 * 1152, 128, ln=True, rope="lut", hd=HD_VIT, rope_cols=2304, gemm_split=0, gemm_pp64=0)
+    for q_cols in (1152, 2 * HD_VIT):          # the pre-scaled Q block: 18 whole 64-column tiles, and two heads (tile 128 .. 192 straddles)
+        run_cell(dev, 3, 2048, 3 * 1152, 128, bias=True, rope="lut", hd=HD_VIT, rope_cols=2304, q_cols=q_cols, gemm_split=0, gemm_pp64=0)
+        run_cell(dev, 3, 2048, 3 * 1152, 128, ln=True, rope="lut", hd=HD_VIT, rope_cols=2304, q_cols=q_cols, gemm_split=0, gemm_pp64=0)
     for kw in (dict(bias=True, res="sep"), dict(bias=True, res="inplace"), dict(act=R.ACT_SWIGLU),
                dict(bias=True, act=R.ACT_GELU_ERF), dict(bias=True, res="sep", stats=True)):
         run_cell(dev, 3, 1300, 1152, 192, **kw, gemm_split=0, gemm_pp64=0)
@@ -526,8 +547,31 @@ def test_split_body(dev, M, N, K):
              dict(ln=True), dict(ln=True, act=R.ACT_GELU_TANH), dict(ln=True, rope="sep", rope_cols=rc)]
     if N == 3456:
         cells = cells[6:10]
+        # q_scale (cogs_gemm_fused) on the encoder's own QKV shape: the Q block of 16 heads of 72 ends on a 64-column tile
+        # boundary (1152); two heads (144) end inside the tile 128 .. 192, which must leave the lean path
+        for q_cols in (1152, 2 * HD_VIT):
+            cells += [dict(bias=True, rope="inter", rope_cols=rc, hd=HD_VIT, q_cols=q_cols),
+                      dict(bias=True, rope="sep", rope_cols=rc, hd=HD_VIT, q_cols=q_cols),
+                      dict(ln=True, rope="inter", rope_cols=rc, hd=HD_VIT, q_cols=q_cols),
+                      dict(bias=True, rope="inter", hm=True, q_cols=q_cols, **hm_kw),
+                      dict(ln=True, rope="inter", hm=True, q_cols=q_cols, **hm_kw)]
     for kw in cells:
         run_cell(dev, 5, M, N, K, **kw)
+
+
+# ----------------------------------------------------------------------------------------------------------- q_scale, M > 1
+@pytest.mark.gpu
+@pytest.mark.parametrize("body,M,sw", [(1, 257, {}), (2, 777, {}), (4, 1300, dict(gemm_split=0))])
+@pytest.mark.parametrize("q_cols", [576, 144])
+def test_q_scale_on_the_prompt_bodies(dev, body, M, sw, q_cols):
+    """the Q pre-scale of the rotary epilogues (five places in csrc/gemm_epilogue.h) through cogs_gemm_fused, at the factor the
+    model passes for head_dim 72: q_cols = 576 (8 heads) ends on a 64-column tile boundary, q_cols = 144 (2 heads) inside the
+    tile 128 .. 192, which has to leave the lean path. Row-major with both table forms and with the LN fold; head-major (the
+    encoder's own QKV GEMM: 3 blocks of 8 heads of 72) with bias and with the LN fold"""
+    for kw in (dict(bias=True, rope="inter"), dict(bias=True, rope="sep"), dict(ln=True, rope="inter")):
+        run_cell(dev, body, M, 1152, 192, hd=HD_VIT, rope_cols=720, q_cols=q_cols, **kw, **sw)
+    for kw in (dict(bias=True), dict(ln=True)):
+        run_cell(dev, body, M, 3 * 576, 192, rope="inter", hm=True, hd=HD_VIT, rope_cols=1152, q_cols=q_cols, **kw, **sw)
 
 
 # ----------------------------------------------------------------------------------------------------------- Qwen2 prompts

@@ -12,6 +12,7 @@ import torch
 
 import attn_reference as AR
 import gemm_reference as R
+import gemv_reference as G
 
 pytestmark = pytest.mark.gpu
 
@@ -45,11 +46,10 @@ def _operands(dev, M, N, K, seed):
 
 
 def run_rows_cell(dev, M, N, K, *, bias=False, res=None, act=R.ACT_NONE, out_f32=False, rope=False, rope_cols=0, q_cols=0,
-                  seed=1, cols=None):
+                  q_scale=0.125, seed=1, cols=None):
     """one cogs_gemm_rows; every output element (or the columns `cols`) against its own fp64 band; the guard rows above and
     below C and the guard columns beside it keep their bits. res: None | "sep" | "inplace"; rope: per-row interleaved table;
-    q_cols > 0: q_scale = 2^-3 on the columns below it (a power of two commutes with every rounding: the reference runs on
-    pre-scaled columns, as tests/test_gpu_fp8.py::run_cell does)"""
+    q_cols > 0: q_scale on the columns below it (2^-3 unless given: an exact multiply, which adds nothing to the band)"""
     from cogstream_amd import ops
     a, w, g = _operands(dev, M, N, K, seed)
     swiglu = act == R.ACT_SWIGLU
@@ -78,14 +78,10 @@ def run_rows_cell(dev, M, N, K, *, bias=False, res=None, act=R.ACT_NONE, out_f32
         kw["residual"] = cview
     sel = slice(None) if cols is None else cols
     acc, bound = R.product_and_bound(a, w[sel])
-    bias_ref = bias_t
     if q_cols:
-        kw.update(q_scale=0.125, q_cols=q_cols)
-        colscale = torch.where(torch.arange(N, device=dev) < q_cols, 0.125, 1.0).double()
-        acc, bound = acc * colscale[None, sel], bound * colscale[None, sel]
-        bias_ref = bias_t.double() * colscale if bias_t is not None else None
+        kw.update(q_scale=q_scale, q_cols=q_cols)
     guard = _bits(cbuf)[~inside].clone()
-    ref, tol = R.epilogue(acc, bound, cols=cols, bias=bias_ref, rope=rope_r, act=act,
+    ref, tol = R.epilogue(acc, bound, cols=cols, bias=bias_t, rope=rope_r, q_scale=q_scale if q_cols else None, q_cols=q_cols, act=act,
                           residual=res_t[:, sel] if res_t is not None else None, out_f32=out_f32, out_dtype=odt)
     ops.gemm_rows(a, w, **kw)
     torch.cuda.synchronize()
@@ -109,11 +105,12 @@ def test_gemm_rows_k_edges(dev, M):
         run_rows_cell(dev, M, 256, K, seed=K + M)
 
 
-@pytest.mark.parametrize("epi", ["qkv", "residual", "residual in place", "swiglu", "fp32"])
+@pytest.mark.parametrize("epi", ["qkv", "qkv model scale", "residual", "residual in place", "swiglu", "fp32"])
 def test_gemm_rows_epilogues(dev, epi):
     """M = 7, in the k-split form (N = 640) and in the one-block-per-wave form (N > 16384)"""
-    for N in (5 * HD, 129 * HD if epi == "qkv" else 16388):
+    for N in (5 * HD, 129 * HD if epi.startswith("qkv") else 16388):
         kw = {"qkv": dict(bias=True, rope=True, rope_cols=N - HD, q_cols=N - 2 * HD),      # Q heads | one K head | one V head
+              "qkv model scale": dict(bias=True, rope=True, rope_cols=N - HD, q_cols=N - 2 * HD, q_scale=G.model_q_scale(HD)),
               "residual": dict(res="sep"), "residual in place": dict(res="inplace"),
               "swiglu": dict(act=R.ACT_SWIGLU), "fp32": dict(out_f32=True)}[epi]
         run_rows_cell(dev, 7, N, 192, seed=3, **kw)

@@ -64,7 +64,7 @@ def run_cell(dev, M, N, K, *, bias=False, res=None, act=R.ACT_NONE, out_f32=Fals
     (b) the two C buffers hold the same bits,
     (c) the guards keep their tracer bits.
     res: None | "sep" | "inplace"; rope: per-row interleaved table; q_cols > 0: q_scale = 2^-3 on the columns below it (a power
-    of two commutes with every rounding: the reference runs on pre-scaled columns, as test_gpu_rows.py::run_rows_cell does)"""
+    of two commutes with every rounding: the reference runs on pre-scaled columns; test_gpu_rows.py has the cell at the model's factor)"""
     from cogstream_amd import ops
     a, codes, scale, wd, g = _operands(dev, M, N, K, seed)
     swiglu = act == R.ACT_SWIGLU
